@@ -1,7 +1,19 @@
 #!/usr/bin/env python
 """bench.py -- blocks tuned per second on MI355X (BASELINE.json metric), one process per GPU.
 
-    python bench.py [--gpus N --steps K --warmup W]            (N>1: launched by torch.distributed.run, RCCL)
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]   (N>1: launched by torch.distributed.run, RCCL)
+
+A plain run sets up, warms up (W steps), times K steps, writes the last timed step's outputs when `--dump-outputs DIR` is given and
+prints the JSON line: `value` (blocks/s), `ms_per_step`, `config`, `loss` and the live roofline objects (device events attached to the
+timed dispatches themselves, no run of their own).  `--full` adds everything else the line used to carry: the CPU baselines, and at
+the default Llama-3-8B configuration the other paths (`variants`), the OPT-125M object and the live parity checks (`parity`), with
+the nested / flat copies of them under `config`, `roofline` and `cpu_baseline`.
+
+`--dump-outputs DIR`: what a caller of the timed path receives from its last step -- the packed layers' tensors (`packed.<layer>.<key>`),
+the best rounding / scale parameters (`best.<layer>.<key>`), the block's fp and quantised outputs (`fp_out`, `q_out`) and
+`loss` ([init, best, best_iter]) -- as DIR/<name>.npy, integers as float64 (exact), the rest as float32.  Together at most
+DUMP_BUDGET_BYTES: a tensor larger than its share is written as a fixed seeded sample of its flattened elements (the same positions
+run after run).  Inputs are seeded, so two builds can be compared output for output with the same arguments.
 
 A "step" is ONE transformer block tuned end to end through the hot path -- reference fp forward of the 128
 calibration samples, 200 sign-SGD iterations (fake-quant forward, block forward/backward against the cached
@@ -22,8 +34,8 @@ independent): RCCL broadcast of the shared calibration activations, pipelined po
 rank tunes its K blocks, packed results gathered on rank 0.  No per-iteration collective.  value = N*K blocks / max-over-
 ranks time.  `--data-parallel` is the strong-scaling alternative inside one block.
 
-Objects on the JSON line (N=1).  The driver's record keeps `config`, `roofline` and `cpu_baseline`, so everything a reader needs is
-(also) nested under those three (`nest_for_the_driver`):
+Objects on the JSON line (N=1; `cpu_baseline` and everything but the live roofline only with `--full`).  The driver's record keeps
+`config`, `roofline` and `cpu_baseline`, so everything a reader needs is (also) nested under those three (`nest_for_the_driver`):
   roofline          quant-forward kernel (K1, `k_int_fwd_flat`): algorithmic bytes (8 B/elem + 12 B/group) / the
                     kernel's own average duration, measured live inside the timed region with device start/stop events
                     attached to each dispatch (`ar_profile_*`, hipExtLaunchKernelGGL) -- the same quantity rocprofv3
@@ -68,6 +80,7 @@ WORKLOADS = {
 }
 SCHEMES = ("W4A16", "W2A16G32", "MXFP4", "NVFP4", "MXFP4_W", "NVFP4_W", "INT8", "INT4")     # INT8 / INT4: per-row weights, per-token activations
 HBM_PEAK_GBPS = 8000.0   # MI355X HBM3E spec peak (MI355X_MICROARCH.md); ~6300 GB/s is the measured copy ceiling
+DUMP_BUDGET_BYTES = 60 * 2 ** 20   # --dump-outputs: all arrays together (under 64 MB)
 
 
 def build_block(w, bits, gs, sym, device, seed, attn="sdpa", scheme=None):
@@ -346,6 +359,47 @@ def read_traffic(kernel, abytes=None):
         return None
 
 
+def step_outputs(stats, packed, result):
+    """{name: tensor}: what a caller of the timed path receives from one step (see the module docstring, --dump-outputs)."""
+    fp_out, q_out, best = result
+    loss = [stats.get(k) for k in ("init_loss", "best_loss", "best_iter")]
+    arrays = {"loss": torch.tensor([float("nan") if v is None else float(v) for v in loss], dtype=torch.float64)}
+    for n, m in packed.items():
+        for k, t in m.state_dict().items():
+            arrays[f"packed.{n}.{k}"] = t
+    for n, params in (best or {}).items():
+        for k, t in params.items():
+            if isinstance(t, torch.Tensor):
+                arrays[f"best.{n}.{k}"] = t
+    arrays["fp_out"] = fp_out
+    if q_out is not None:
+        arrays["q_out"] = q_out
+    return arrays
+
+
+def dump_outputs(outdir, arrays, budget=DUMP_BUDGET_BYTES, seed=0):
+    """Write {name: tensor} as outdir/<name>.npy: integer and float64 tensors as float64 (exact), the others as float32.  Every array
+    gets an equal share of `budget`; a larger tensor is written as `cap` elements of its flattened form at positions drawn with a
+    generator seeded by `seed` (the same positions for the same size).  -> {"arrays", "sampled", "bytes"}"""
+    import numpy as np
+
+    os.makedirs(outdir, exist_ok=True)
+    cap = max(1, budget // (8 * max(len(arrays), 1)))
+    rec = {"dir": outdir, "arrays": len(arrays), "sampled": 0, "bytes": 0}
+    for name, t in arrays.items():
+        t = t.detach().reshape(-1)
+        wide = not t.is_floating_point() or t.dtype == torch.float64
+        if t.numel() > cap:
+            idx = torch.randint(0, t.numel(), (cap,), generator=torch.Generator().manual_seed(seed)).sort().values
+            t = t[idx.to(t.device)]
+            rec["sampled"] += 1
+        a = t.to(torch.float64 if wide else torch.float32).cpu().numpy()
+        np.save(os.path.join(outdir, name + ".npy"), a)
+        rec["bytes"] += a.nbytes
+    assert rec["bytes"] <= budget, rec
+    return rec
+
+
 class Bench:
     """One workload on this rank's GPU: block, synthetic calibration data, quantizer; `timed(steps, warmup)` -> dict."""
 
@@ -418,13 +472,14 @@ class Bench:
                 if p.data.shape == self.master[n].shape:
                     p.data = self.master[n].clone()
 
-    def one_block(self):
+    def one_block(self, keep=False):
+        """-> (stats, packed, result): result = compress_block's (fp_out, q_out, best) when `keep`, else None (released here)."""
         from auto_round_amd.export import pack_block
 
         self.restore()                                      # "dispatch_block": fresh fp weights in HBM
-        self.quantizer.compress_block(self.layer, self.X, self.others, input_ids=self.token_ids)
+        result = self.quantizer.compress_block(self.layer, self.X, self.others, input_ids=self.token_ids)
         packed = pack_block(self.layer)                     # final low-bit packing kernel, GPTQ-order int32 words
-        return self.quantizer.last_stats, packed
+        return self.quantizer.last_stats, packed, (result if keep else None)
 
     def timed(self, steps, warmup, barrier, profile=True):
         from auto_round_amd import ops
@@ -442,13 +497,14 @@ class Bench:
             ops.profile_enable(True)
         t0 = time.perf_counter()
         stats = None
-        for _ in range(steps):
-            stats, _ = self.one_block()
+        for i in range(steps):
+            stats, packed, result = self.one_block(keep=i == steps - 1)
         barrier()
         elapsed = time.perf_counter() - t0
         if profile:
             ops.profile_enable(False)
         self.qcfg.hip_graph = auto_graph
+        self.last_outputs = (stats, packed, result)        # the last timed step's outputs (--dump-outputs)
         return elapsed, stats
 
     def rooflines(self):
@@ -539,12 +595,20 @@ def main():
                     help="replay each tuning iteration as one captured hipGraph even while per-dispatch kernel timing is on (the roofline "
                          "objects then only see iteration 0 of every block); without the flag: automatic for small blocks when timing is off")
     ap.add_argument("--no-hip-graph", action="store_true", help="keep every tuning iteration host-driven (A/B against the captured form)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the CPU baselines and, at the default Llama-3-8B configuration, "
+                         "the variants, opt125m and parity objects (off: set up, warm up, time the steps, print the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32 / float64, at most 60 MiB in all, large "
+                         "tensors as a fixed seeded sample)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
     ap.add_argument("--no-kernel-timing", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the opt125m and variants objects")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the opt125m, variants and parity objects")
     ap.add_argument("--gemm-mfma", type=int, default=16, choices=[16, 32],
                     help="A/B knob: the first-party GEMM kernels on v_mfma_f32_16x16x32_bf16 (default) or on 32x32x16 (rounds 2-4); same bits")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -596,6 +660,8 @@ def main():
 
     dp = bool(args.data_parallel and world > 1)
     sharded = world > 1 and not dp
+    if sharded and args.dump_outputs:
+        raise SystemExit("--dump-outputs: the block-sharded pipeline (N>1 without --data-parallel) tunes a different block on every rank")
     path = "module" if args.no_fused_block else args.path
     if path == "exact" and (dp or WORKLOADS[args.workload]["family"] not in ("llama", "opt")) and not args.force_exact:
         path = "fused"          # exact_rounding covers the Llama and OPT families, one rank per block; everything else: the fused path
@@ -642,6 +708,11 @@ def main():
         if dist is not None:
             dist.broadcast(b.X, src=0)
         elapsed, stats = b.timed(args.steps, args.warmup, barrier, profile=profile)
+    dumped = None
+    if not sharded:
+        if rank == 0 and args.dump_outputs:
+            dumped = dump_outputs(args.dump_outputs, step_outputs(*b.last_outputs))
+        b.last_outputs = None
     if dist is not None:
         t = torch.tensor([elapsed], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -700,9 +771,11 @@ def main():
             out.update(b.rooflines())          # (N > 1: rank 0's own dispatches)
         if multi is not None:
             out["multi_gpu"] = multi
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
         if profile and "roofline_bwd_sgd" in out:       # (also nested: the driver's record keeps `roofline`, not its siblings)
             out["roofline"]["bwd_sgd"] = {k: out["roofline_bwd_sgd"][k] for k in ("kernel", "achieved", "peak", "frac", "traffic", "avg_launch_ms", "launches")}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             try:
                 big = n_w > 50_000_000
                 out["cpu_baseline"] = cpu_baseline(w, b.bits, b.gs, b.sym, S, args.batch_size, args.iters, extrapolate=big, mask=args.mask)
@@ -719,7 +792,7 @@ def main():
                     out["speedup_vs_cpu_reference_quoted"] = out["value"] / ref["value"]
                     if "error" not in out["cpu_baseline"]:
                         out["cpu_baseline"]["reference_quoted"] = ref
-        if world == 1 and default_cfg and args.workload == "llama3-8b" and not args.no_extras:
+        if world == 1 and args.full and default_cfg and args.workload == "llama3-8b" and not args.no_extras:
             del b.X, b.layer, b.master
             torch.cuda.empty_cache()
             try:

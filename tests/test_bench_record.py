@@ -115,3 +115,31 @@ def test_traffic_is_refused_when_the_kernel_sources_changed_since_the_pmc_pass(t
     assert b.read_traffic("k_int_fwd", 101) is None                              # another block size than the one profiled
     (prof / "r06_pmc_traffic.json").write_text(json.dumps(dict(good, sources_sha256="0" * 64)))
     assert b.read_traffic("k_int_fwd") is None                                   # the newest file describes other sources: refused
+
+
+def test_dump_outputs_is_exact_seeded_and_within_budget(tmp_path):
+    """--dump-outputs: integers as float64 (exact), floats as float32, large tensors as a fixed seeded sample, all of it under the
+    budget -- two dumps of the same outputs are equal file for file."""
+    import numpy as np
+    import torch
+
+    b = _bench()
+    packed = {"q_proj": torch.nn.Module()}
+    packed["q_proj"].register_buffer("qweight", torch.arange(-2 ** 31, -2 ** 31 + 4096 * 64, 64, dtype=torch.int32).reshape(64, 64))
+    packed["q_proj"].register_buffer("scales", torch.rand(8, 64).half())
+    best = {"q_proj": {"value": torch.rand(1 << 16), "min_scale": torch.rand(512)}}
+    fp = torch.randn(4, 8, 64).bfloat16()
+    arrays = b.step_outputs({"init_loss": 2.0, "best_loss": 1.0, "best_iter": 7}, packed, (fp, fp * 2, best))
+    assert set(arrays) == {"loss", "packed.q_proj.qweight", "packed.q_proj.scales", "best.q_proj.value", "best.q_proj.min_scale", "fp_out", "q_out"}
+    budget = 8 * len(arrays) * 5000                    # 5000 elements per array: only best.q_proj.value (65536) is sampled
+    r1 = b.dump_outputs(str(tmp_path / "a"), arrays, budget=budget)
+    r2 = b.dump_outputs(str(tmp_path / "b"), arrays, budget=budget)
+    assert r1["arrays"] == 7 and r1["sampled"] == 1 and r1["bytes"] == r2["bytes"] <= budget
+    for name in arrays:
+        a1, a2 = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert np.array_equal(a1, a2), name
+        assert a1.dtype == (np.float64 if name in ("loss", "packed.q_proj.qweight") else np.float32), name
+    assert np.array_equal(np.load(tmp_path / "a" / "packed.q_proj.qweight.npy"), packed["q_proj"].qweight.reshape(-1).double().numpy())
+    assert np.array_equal(np.load(tmp_path / "a" / "loss.npy"), [2.0, 1.0, 7.0])
+    v = np.load(tmp_path / "a" / "best.q_proj.value.npy")
+    assert v.shape == (5000,) and np.isin(v, best["q_proj"]["value"].numpy()).all()

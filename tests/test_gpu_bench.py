@@ -93,3 +93,29 @@ def test_two_ranks_shard_blocks_on_the_exact_path():
     d = _last_json(r.stdout)
     assert d["n_gpus"] == 2 and d["scaling"] == "weak" and d["value"] > 0 and d["config"]["path"] == "exact" and d["config"]["exact_rounding"] is True
     assert d["multi_gpu"]["blocks_tuned_per_rank"] == [2, 2]
+
+
+def test_plain_run_is_lean_dumps_its_outputs_and_full_adds_the_rest(tmp_path):
+    """A plain run prints the headline without the CPU baseline and writes the last timed step's outputs with --dump-outputs
+    (float32 / float64 .npy, under 64 MB); --full adds the CPU baseline."""
+    import numpy as np
+
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--dump-outputs", str(out)] + TINY_LLAMA[:-1],
+                       cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = _last_json(r.stdout)
+    assert d["steps"] == 2 and d["ms_per_step"] > 0 and "cpu_baseline" not in d and "variants" not in d
+    files = {p.name: p for p in out.iterdir()}
+    assert {"loss.npy", "fp_out.npy", "q_out.npy", "packed.self_attn.q_proj.qweight.npy", "best.mlp.down_proj.value.npy"} <= set(files)
+    assert d["dumped_outputs"]["arrays"] == len(files) and sum(p.stat().st_size for p in files.values()) < 64e6
+    for p in files.values():
+        a = np.load(p)
+        assert a.dtype in (np.float32, np.float64) and a.size > 0 and np.isfinite(a).all(), p.name
+    loss = np.load(files["loss.npy"])
+    assert loss[0] == d["loss"]["init"] and loss[1] == d["loss"]["best"] and loss[2] == d["loss"]["best_iter"]
+    r = subprocess.run([sys.executable, "bench.py", "--steps", "1", "--warmup", "1", "--full"] + TINY_LLAMA[:-1], cwd=ROOT,
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = _last_json(r.stdout)
+    assert d["steps"] == 1 and d["cpu_baseline"]["value"] > 0 and d["cpu_baseline"]["kind"] == "port"
