@@ -34,7 +34,7 @@ enum { AR_DT_BF16 = 0, AR_DT_F16 = 1, AR_DT_F32 = 2 };
 enum { AR_OK = 0, AR_ERR_UNSUPPORTED = -1 };
 
 /* ABI version of this header; bump on any signature change.  ar_abi_version() of the loaded library must equal it. */
-#define AR_ABI_VERSION 27
+#define AR_ABI_VERSION 28
 int ar_abi_version(void);
 /* Human-readable text for a non-zero return code of any function below. */
 const char* ar_error_string(int code);
@@ -415,21 +415,21 @@ int ar_gemm_nt(const void* A, const void* B, void* C, int64_t M, int64_t N, int6
  * M / 256 + n_groups row tiles (every group may end in a partial tile); workgroups past the last real tile exit.  Deterministic. */
 int ar_gemm_nt_grouped(const void* A, const void* B, void* C, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc,
                        const int32_t* row_off, const int64_t* b_off, int n_groups, ar_stream_t stream);
-/* experiment knob of the two entry points above for tools/gpu/r05_gemm_nt*_probe.py (binding hygiene): variant 3 = the kernel on
- * v_mfma_f32_16x16x32_bf16 (default since round 5), 0 = on 32x32x16 with the LDS-DMA pieces issued between the MFMAs, 1 = 32x32x16 with
- * the pieces at the end of the fragment-read part of every second phase, 2 = 32x32x16 with one wave per SIMD and 128 x 128 wave tiles;
- * all four produce identical bits; -1 keeps.  Returns the variant in use. */
+/* A/B knob of the two entry points above (binding hygiene; the tests' bit-for-bit cross-check, tools/gpu/r05_gemm_nt*_probe.py):
+ * variant 3 = the kernel on v_mfma_f32_16x16x32_bf16 (default since round 5), 0 = the same kernel on v_mfma_f32_32x32x16_bf16;
+ * both produce identical bits.  Any other value (-1 by convention) keeps the setting.  Returns the variant in use. */
 int ar_gemm_nt_config(int variant);
 /* measurement hygiene (tools/gpu/r05_gemm_nt_trace.py; no reference counterpart): ar_gemm_nt with s_memtime bookkeeping -- trace receives
  * [row tiles * column tiles][8 waves][8] uint64: shader cycles a wave spent, summed over its phases, in the fragment-read part, parked at
  * the barrier after it, in the MFMA part, parked at the barrier after it; the cycles of the whole K loop; the number of phases; the whole
- * K loop in ticks of the constant 100 MHz counter (s_memrealtime: cycles / ticks * 100 MHz = the shader clock the kernel ran at); 0. */
+ * K loop in ticks of the constant 100 MHz counter (s_memrealtime: cycles / ticks * 100 MHz = the shader clock the kernel ran at); 0.
+ * variant: 0 or 3, as in ar_gemm_nt_config; any other value AR_ERR_UNSUPPORTED. */
 int ar_gemm_nt_trace(const void* A, const void* B, void* C, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc,
                      unsigned long long* trace, int variant, ar_stream_t stream);
-/* experiment knobs of the kernel above for tools/gemm_dw_probe.py (binding hygiene; -1 keeps a value): sem = lane->piece rule
- * of the transposing LDS read (1 | 2), order = tile order (0 identity, 1 XCD chunks, 2 XCD 2x8 patches); sem 20 | 21 = hybrid split of the
- * last partial round off | on; sem 32 | 30 | 31 = the kernel on v_mfma_f32_16x16x32_bf16 (default since round 5) | on 32x32x16 (rounds
- * 2-4) | on 32x32x16 with the LDS-DMA issued outside the MFMA cluster -- all three produce identical bits.  Returns sem*10+order. */
+/* A/B knobs of the weight-gradient GEMM (ar_gemm_dw and its _ex / _sk / _grouped forms; binding hygiene): sem 20 | 21 = hybrid split
+ * of the last partial round off | on; sem 32 | 30 = the kernel on v_mfma_f32_16x16x32_bf16 (default since round 5) | on
+ * v_mfma_f32_32x32x16_bf16 (rounds 2-4) -- identical bits; order = tile order (0 identity, 1 XCD chunks, 2 XCD 2x8 patches: the default).
+ * Any other value of either argument (-1 by convention) keeps the setting.  Returns the MFMA shape code in use, 30 or 32. */
 int ar_gemm_dw_config(int sem, int order);
 
 /* ---- causal attention forward (hand-written MFMA flash attention, gfx950) ------------------------------------------
@@ -493,12 +493,6 @@ int ar_attn_bwd_exact(const void* Q, const void* K, const void* V, const void* O
                       int64_t valid_len, int64_t q_bs, int64_t q_hs, int64_t q_ts, int64_t k_bs, int64_t k_hs, int64_t k_ts, int64_t v_bs,
                       int64_t v_hs, int64_t v_ts, int64_t o_bs, int64_t o_hs, int64_t o_ts, int64_t do_bs, int64_t do_hs, int64_t do_ts,
                       int64_t lddq, int64_t lddk, int64_t lddv, void* workspace, int64_t workspace_bytes, ar_stream_t stream);
-
-/* Launch form of ar_attn_fwd_exact / ar_attn_bwd_exact (binding hygiene: a tuning knob for A/B measurements, results are identical
- * in every form -- the per-row arithmetic does not depend on how many rows a workgroup owns).  Bits 0-1 forward, bits 2-3 backward:
- * 0 default, 1 workgroups of 4 waves (128 own rows), 2 workgroups of 8 waves (256), 3 (backward, head size 128) dK and dV in one
- * kernel on one wave per SIMD -- the default there.  cfg < 0 only reads.  -> the previous value. */
-int ar_attn_exact_config(int cfg);
 
 /* ---- causal attention backward, head size 64 (deterministic: two MFMA kernels, no float atomics) ---------------------------
  * replaces: autograd of the same attention call -- torch's aten::_scaled_dot_product_efficient_attention_backward, i.e. aiter's

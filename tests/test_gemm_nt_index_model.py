@@ -21,8 +21,5 @@ def test_the_model_restates_the_kernels_formulas():
     for frag in ("pc ^ ((4 * j + (lane >> 4)) & 7)", "l31 * 128 + 16 * ((4 * ah + 2 * u + h) ^ s)", "(l31 >> 1) & 7",
                  "lds0 + 65536 + (wc >> 1) * 32768 + (wc & 1) * 8192 + X", "lds0 + wr * 32768 + wc * 32 * 128",
                  # the 16x16x32 form
-                 "l15 * 128 + 16 * ((4 * ah + kg) ^ s)", "adB16[ah] = lds0 + 65536 + (wc >> 1) * 32768 + (wc & 1) * 8192 + X;",
-                 # nt2
-                 "const int row = wave * 64 + 8 * j + (lane >> 3);", "lds0 + (wave >> 1) * 32768 + (wave & 1) * 64 * 128", "l31 * 128 + 16 * ((2 * u + h) ^ s)",
-                 "adB[u] = lds0 + 65536 + wc * 32768 + X;"):
+                 "l15 * 128 + 16 * ((4 * ah + kg) ^ s)", "adB16[ah] = lds0 + 65536 + (wc >> 1) * 32768 + (wc & 1) * 8192 + X;"):
         assert frag in src, frag

@@ -1,4 +1,5 @@
-"""Launch the weight-gradient GEMM variants a few times on one shape (for rocprofv3 --pmc passes; see gpurun_variants/*.sh)."""
+"""Launch the library's product and the weight-gradient GEMM on its two MFMA shapes (ar_gemm_dw_config 32: 16x16x32, the default;
+30: 32x32x16) a few times on one shape, for rocprofv3 --pmc passes."""
 import os
 import sys
 
@@ -17,7 +18,8 @@ out = torch.empty(M, N, dtype=torch.bfloat16, device=dev)
 lib = load()
 for _ in range(3):
     torch.mm(dY.t(), X, out=out)
-    for code in (11, 17):
+    for code in (32, 30):
         lib.ar_gemm_dw_config(code, 2)
         ops.gemm_dw(dY, X, out)
+lib.ar_gemm_dw_config(32, 2)
 torch.cuda.synchronize()

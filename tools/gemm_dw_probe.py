@@ -1,6 +1,7 @@
 """A/B of the hand-written MFMA weight-gradient GEMM (ar_gemm_dw, csrc/ar_gemm.hip) against hipBLASLt's torch.mm(dY.t(), X) on
 the Llama-3-8B layer shapes at K = 8 x 2048 tokens: correctness (vs an fp32 product), kernel time (interleaved rounds, device
-events), PFLOP/s.  Prints one JSON object per (shape, variant)."""
+events), PFLOP/s.  Variants: the two MFMA shapes of the shipped kernel, v6 (16x16x32, the default) and v3 (32x32x16), each with a tile
+order (name:order).  Prints one JSON object per (shape, variant)."""
 import argparse
 import json
 import os
@@ -30,17 +31,17 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", default="q_o,gate_up,down,qkv_merged,kv")
     ap.add_argument("--K", type=int, default=16384)
-    ap.add_argument("--variants", default="v1_staggered:2,v3:2")       # kernel:order
-    ap.add_argument("--ablate", action="store_true", help="also time the v1 ablations (no DMA / no reads / MFMA only): garbage outputs")
+    ap.add_argument("--variants", default="v6:2,v3:2")       # kernel:order
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--reps", type=int, default=5)
     args = ap.parse_args()
     dev = torch.device("cuda")
     lib = load()
     torch.manual_seed(0)
+    KERNELS = {"v3": 30, "v6": 32}
     # correctness first, on a shape small enough for an fp32 reference: asymmetric random operands
-    for sem in (1, 2):
-        lib.ar_gemm_dw_config(sem, 2)
+    for kname, code in KERNELS.items():
+        lib.ar_gemm_dw_config(code, 2)
         K, M, N = 256, 512, 256
         dY = torch.randn(K, M, device=dev).to(torch.bfloat16)
         X = torch.randn(K, N, device=dev).to(torch.bfloat16)
@@ -49,12 +50,9 @@ def main():
         ref = dY.float().t() @ X.float()
         err = (out.float() - ref).abs().max().item()
         exact = (out == ref.to(torch.bfloat16)).float().mean().item()
-        print(json.dumps({"check": "small", "sem": sem, "took_kernel": ok, "max_abs_err": err, "frac_equal_to_rounded_fp32": exact}), flush=True)
-    lib.ar_gemm_dw_config(1, 2)
-    KERNELS = {"v0": 10, "v1_staggered": 11, "v1_lockstep": 12, "v3": 17, "v4_l4": 18, "v4_l8": 19}
-    ABLATIONS = {"abl_no_dma": 14, "abl_no_dma_no_reads": 15, "abl_mfma_only": 16}
-    # accumulate + strided operands (column slices of wider buffers), multi-tile, all tile orders, every kernel
-    for kname, code in list(KERNELS.items()):
+        print(json.dumps({"check": "small", "kernel": kname, "took_kernel": ok, "max_abs_err": err, "frac_equal_to_rounded_fp32": exact}), flush=True)
+    # accumulate + strided operands (column slices of wider buffers), multi-tile, both kernels
+    for kname, code in KERNELS.items():
         for order in (2,):
             lib.ar_gemm_dw_config(code, order)
             K, M, N = 512, 1024, 2048
@@ -70,9 +68,6 @@ def main():
             print(json.dumps({"check": "strided+accumulate", "kernel": kname, "order": order, "max_rel_err": err,
                               "frac_equal_to_rounded_fp32": exact}), flush=True)
     wanted = [v for v in args.variants.split(",")]
-    if args.ablate:
-        KERNELS = dict(KERNELS, **ABLATIONS)
-        wanted += [f"{k}:2" for k in ABLATIONS]
     for name in args.shapes.split(","):
         M, N = SHAPES[name]
         K = args.K
@@ -108,6 +103,7 @@ def main():
             print(json.dumps({"shape": name, "M": M, "N": N, "K": K, "impl": k, "ms_median": ms, "ms_min": min(ts),
                               "pflops": flops / ms / 1e12, "max_abs_diff_vs_hipblaslt": diffs.get(k, (0.0, 1.0))[0],
                               "frac_bit_equal_to_hipblaslt": diffs.get(k, (0.0, 1.0))[1], "mean_abs_out": scale}), flush=True)
+    lib.ar_gemm_dw_config(32, 2)
 
 
 if __name__ == "__main__":

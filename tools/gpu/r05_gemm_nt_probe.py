@@ -177,8 +177,10 @@ def grouped_case(counts, N, K, gen, Mdw=None):
 
 
 def ab_variants(gen):
-    """A/B of where the LDS-DMA pieces are issued (between the MFMAs = 0 / at the end of the fragment-read part = 1), for the NT kernel
-    and for the weight-gradient kernel: identical bits between the variants, race screen, interleaved timing rounds."""
+    """A/B of the two MFMA shapes (32x32x16: NT variant 0, weight-gradient code 30; 16x16x32, the default: variant 3, code 32), for the NT
+    kernel and for the weight-gradient kernel: identical bits between the variants, race screen, interleaved timing rounds.  (The round-5
+    A/B of where the LDS-DMA pieces are issued and of the one-wave-per-SIMD kernel, profiles/r05_gemm_nt_probe.json, was made with an
+    earlier version of this function; those forms were removed.)"""
     from auto_round_amd import _lib
 
     lib = _lib.load()
@@ -187,7 +189,7 @@ def ab_variants(gen):
         A, B = rnd((M, K), gen), rnd((N, K), gen, 0.05)
         lib_out = torch.mm(A, B.t())
         outs, rec = {}, dict(shape=name, M=M, N=N, K=K)
-        for v in (0, 1, 2):
+        for v in (0, 3):
             lib.ar_gemm_nt_config(v)
             o = torch.full((M, N), float("nan"), dtype=torch.bfloat16, device="cuda")
             ops.gemm_nt(A, B, o)
@@ -199,27 +201,28 @@ def ab_variants(gen):
             outs[v] = o
             rec[f"v{v}_bits_differ_from_library"] = bits_diff(o, lib_out)
             rec[f"v{v}_repeat_runs_differing"] = flaky
-        t = {0: [], 1: [], 2: [], "lib": []}
+        t = {0: [], 3: [], "lib": []}
         o = torch.empty((M, N), dtype=torch.bfloat16, device="cuda")
         for _ in range(4):
-            for v in (0, 1, 2):
+            for v in (0, 3):
                 lib.ar_gemm_nt_config(v)
                 t[v].append(timeit(lambda: ops.gemm_nt(A, B, o), rounds=1, inner=10)["ms_min"])
             t["lib"].append(timeit(lambda: torch.mm(A, B.t(), out=o), rounds=1, inner=10)["ms_min"])
         fl = 2.0 * M * N * K
         med = lambda x: sorted(x)[len(x) // 2]  # noqa: E731
-        rec.update(v0_ms=med(t[0]), v1_ms=med(t[1]), v2_ms=med(t[2]), lib_ms=med(t["lib"]), v0_pflops=fl / med(t[0]) / 1e12, v1_pflops=fl / med(t[1]) / 1e12,
-                   v2_pflops=fl / med(t[2]) / 1e12, lib_pflops=fl / med(t["lib"]) / 1e12)
+        rec["variants_bits_differ"] = bits_diff(outs[0], outs[3])
+        rec.update(v0_ms=med(t[0]), v3_ms=med(t[3]), lib_ms=med(t["lib"]), v0_pflops=fl / med(t[0]) / 1e12, v3_pflops=fl / med(t[3]) / 1e12,
+                   lib_pflops=fl / med(t["lib"]) / 1e12)
         print(json.dumps(rec), flush=True)
         out["nt"].append(rec)
-    lib.ar_gemm_nt_config(0)
+    lib.ar_gemm_nt_config(3)
     for name, M, N, K in [("o dW", 4096, 4096, 16384), ("qkv merged dW", 6144, 4096, 16384), ("down dW", 4096, 14336, 16384), ("gate dW", 14336, 4096, 16384),
                           ("gate|up merged dW", 28672, 4096, 16384)]:
         dY, X = rnd((K, M), gen, 0.01), rnd((K, N), gen)
         rec = dict(shape=name, M=M, N=N, K=K)
         outs = {}
-        for v in (0, 1):
-            lib.ar_gemm_dw_config(30 + v, -1)
+        for v in (30, 32):
+            lib.ar_gemm_dw_config(v, -1)
             o = torch.full((M, N), float("nan"), dtype=torch.bfloat16, device="cuda")
             ops.gemm_dw(dY, X, o, split=False)
             flaky = 0
@@ -230,23 +233,23 @@ def ab_variants(gen):
             outs[v] = o
             rec[f"v{v}_repeat_runs_differing"] = flaky
             rec[f"v{v}_nan"] = int(torch.isnan(o.float()).sum())
-        rec["variants_bits_differ"] = bits_diff(outs[0], outs[1])
-        t = {(0, False): [], (1, False): [], (0, True): [], (1, True): [], "lib": []}
+        rec["variants_bits_differ"] = bits_diff(outs[30], outs[32])
+        t = {(30, False): [], (32, False): [], (30, True): [], (32, True): [], "lib": []}
         o = torch.empty((M, N), dtype=torch.bfloat16, device="cuda")
         for _ in range(4):
-            for v in (0, 1):
-                lib.ar_gemm_dw_config(30 + v, -1)
+            for v in (30, 32):
+                lib.ar_gemm_dw_config(v, -1)
                 for sp in (False, True):
                     t[(v, sp)].append(timeit(lambda: ops.gemm_dw(dY, X, o, split=sp), rounds=1, inner=6)["ms_min"])
             t["lib"].append(timeit(lambda: torch.mm(dY.t(), X, out=o), rounds=1, inner=6)["ms_min"])
         fl = 2.0 * M * N * K
         med = lambda x: sorted(x)[len(x) // 2]  # noqa: E731
-        rec.update(v0_one_pass_ms=med(t[(0, False)]), v1_one_pass_ms=med(t[(1, False)]), v0_own_plan_ms=med(t[(0, True)]), v1_own_plan_ms=med(t[(1, True)]),
-                   lib_ms=med(t["lib"]), v0_one_pass_pflops=fl / med(t[(0, False)]) / 1e12, v1_one_pass_pflops=fl / med(t[(1, False)]) / 1e12,
-                   v0_own_plan_pflops=fl / med(t[(0, True)]) / 1e12, v1_own_plan_pflops=fl / med(t[(1, True)]) / 1e12, lib_pflops=fl / med(t["lib"]) / 1e12)
+        rec.update(v30_one_pass_ms=med(t[(30, False)]), v32_one_pass_ms=med(t[(32, False)]), v30_own_plan_ms=med(t[(30, True)]), v32_own_plan_ms=med(t[(32, True)]),
+                   lib_ms=med(t["lib"]), v30_one_pass_pflops=fl / med(t[(30, False)]) / 1e12, v32_one_pass_pflops=fl / med(t[(32, False)]) / 1e12,
+                   v30_own_plan_pflops=fl / med(t[(30, True)]) / 1e12, v32_own_plan_pflops=fl / med(t[(32, True)]) / 1e12, lib_pflops=fl / med(t["lib"]) / 1e12)
         print(json.dumps(rec), flush=True)
         out["dw"].append(rec)
-    lib.ar_gemm_dw_config(30, -1)
+    lib.ar_gemm_dw_config(32, -1)
     return out
 
 
@@ -254,7 +257,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--quick", action="store_true")
-    ap.add_argument("--ab", action="store_true", help="only the A/B of the DMA-issue variants (NT and weight-gradient kernels) + the grouped cases")
+    ap.add_argument("--ab", action="store_true", help="only the A/B of the two MFMA shapes (NT and weight-gradient kernels) + the grouped cases")
     args = ap.parse_args()
     gen = torch.Generator(device="cuda").manual_seed(0)
     res = dict(device=torch.cuda.get_device_name(0), torch=torch.__version__, dense=[], timing=[], grouped=[])
@@ -267,10 +270,6 @@ def main():
     if args.ab:
         res["ab"] = ab_variants(gen)
         flush()
-        v2_wins = sum(1 for r in res["ab"]["nt"] if r["v2_ms"] < r["v0_ms"] and r["v2_bits_differ_from_library"] == 0 and r["v2_repeat_runs_differing"] == 0)
-        from auto_round_amd import _lib
-        _lib.load().ar_gemm_nt_config(2 if v2_wins >= 2 else 0)
-        res["grouped_variant"] = 2 if v2_wins >= 2 else 0
     for M, N, K in ([] if args.ab else [(256, 256, 128), (512, 512, 256), (1000, 256, 384), (4096, 1024, 4096), (16384, 4096, 4096), (16384, 4096, 14336)]):
         r = dense_case(M, N, K, gen)
         print(json.dumps(r), flush=True)

@@ -1,6 +1,7 @@
 """Per-phase cycle table of the NT GEMM (csrc/ar_gemm_nt.hip with s_memtime bookkeeping, ar_gemm_nt_trace): where a wave's cycles go --
-fragment reads, parked at the barrier after them, the 16-MFMA cluster (with or without the LDS-DMA issues in it), parked at the barrier
-after it -- for both DMA-issue variants, on Llama-3-8B's o-projection forward shape (16384 x 4096 x 4096, random operands).  VERDICT r04
+fragment reads, parked at the barrier after them, the MFMA cluster with the LDS-DMA issues in it, parked at the barrier after it -- for
+both MFMA shapes (variant 0: 32x32x16, variant 3: 16x16x32), on Llama-3-8B's o-projection forward shape (16384 x 4096 x 4096, random
+operands; the variant-1 rows of profiles/r05_gemm_nt_phase_cycles.json are of the removed form with the DMA issues outside the cluster).  VERDICT r04
 item 2: "... or a per-phase cycle table (s_memtime or PMC) showing where the remaining 40 % of the pipe goes".
 
     python tools/gpu/r05_gemm_nt_trace.py --out gpurun_out/r05/gemm_nt_phase_cycles.json
@@ -19,7 +20,7 @@ from auto_round_amd import _lib  # noqa: E402
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
-    ap.add_argument("--variants", default="0,1,3", help="0 / 1: 32x32x16 with the DMA between the MFMAs / at the end of the read part; 3: 16x16x32")
+    ap.add_argument("--variants", default="0,3", help="0: 32x32x16; 3: 16x16x32")
     args = ap.parse_args()
     lib = _lib.load()
     g = torch.Generator(device="cuda").manual_seed(0)
@@ -47,8 +48,7 @@ def main():
             grp = {"group0_waves_0_3": per[:, :4].mean(dim=(0, 1)).tolist(), "group1_waves_4_7": per[:, 4:].mean(dim=(0, 1)).tolist()}
             allw = per.mean(dim=(0, 1)).tolist()
             clock_ghz = float((t[:, :, 4] / t[:, :, 6].clamp(min=1)).mean()) * 0.1          # shader cycles per 100 MHz tick
-            rec = dict(M=M, N=N, K=K, variant=variant, dma_issue={0: "32x32x16, DMA between the MFMAs (variant 0)", 1: "32x32x16, DMA at the end of the read part of even phases (variant 1)",
-                                                   3: "16x16x32, DMA between the MFMAs (variant 3)"}[variant],
+            rec = dict(M=M, N=N, K=K, variant=variant, dma_issue={0: "32x32x16, DMA between the MFMAs (variant 0)", 3: "16x16x32, DMA between the MFMAs (variant 3)"}[variant],
                        ms_traced=ms, pflops_traced=2.0 * M * N * K / ms / 1e12, phases=int(phases),
                        cycles_per_phase=dict(read_part=allw[0], barrier_after_reads=allw[1], mfma_part=allw[2], barrier_after_mfma=allw[3], whole_phase=allw[4]),
                        by_group=grp, mfma_cycles_if_back_to_back=16 * 32, shader_clock_ghz_during_the_k_loop=clock_ghz,
