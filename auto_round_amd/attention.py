@@ -281,13 +281,6 @@ EXACT_NAME = "mi355x_exact_sdpa"
 exact_state = {"verify": False, "diffs": {}, "calls": 0, "fallbacks": 0, "materialise": False, "key_block": 0}
 
 
-def _count_bits_differ(a: torch.Tensor, b: torch.Tensor) -> int:
-    if a.shape != b.shape or a.dtype != b.dtype:
-        return int(max(a.numel(), b.numel()))
-    it = {2: torch.int16, 4: torch.int32}[a.element_size()]
-    return int((a.contiguous().view(it) != b.contiguous().view(it)).sum())
-
-
 class _ExactAttnFn(torch.autograd.Function):
     """q [B, H, S, D], k / v [B, H / kv_rep, S, D] (un-repeated: transformers' repeat_kv only copies) -> out [B, S, H, D];
     csrc/ar_attn_exact.hip forward and backward.  `ref` (proof runs only): torch's own attention on detached leaves."""
@@ -295,6 +288,7 @@ class _ExactAttnFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, k, v, st, scale, ref):
         from . import ops
+        from .exact_proof import count_diff
 
         kb = int(exact_state.get("key_block") or 0) or ops.attn_key_block_guess(int(q.shape[-1]), int(q.shape[2]))
         got = ops.attn_fwd_exact(q, k, v, st, float(scale), key_block=kb)
@@ -305,12 +299,12 @@ class _ExactAttnFn(torch.autograd.Function):
         ctx.st, ctx.scale, ctx.ref = st, float(scale), ref
         if ref is not None:
             d = exact_state["diffs"]
-            d["out"] = d.get("out", 0) + _count_bits_differ(o, ref[3].detach())
+            d["out"] = d.get("out", 0) + count_diff(o, ref[3].detach())
         return o
 
     @staticmethod
     def backward(ctx, do):
-        from .exact_block import exact_attention_backward
+        from .exact_proof import count_diff, exact_attention_backward      # (lazy: exact_proof does not import this module)
 
         q, k, v, o, lse = ctx.saved_tensors
         if do.stride(-1) != 1 or any(s % 8 for s in do.stride()[:3]):
@@ -320,7 +314,7 @@ class _ExactAttnFn(torch.autograd.Function):
             ql, kl, vl, ro = ctx.ref
             d = exact_state["diffs"]
             for name, mine, want in zip(("dq", "dk", "dv"), (gq, gk, gv), torch.autograd.grad(ro, (ql, kl, vl), do)):
-                d[name] = d.get(name, 0) + _count_bits_differ(mine, want)
+                d[name] = d.get(name, 0) + count_diff(mine, want)
         return gq, gk, gv, None, None, None
 
 

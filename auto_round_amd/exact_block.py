@@ -21,6 +21,8 @@ through this class on the same frozen state and compares the block output and ev
 segment on torch's own ops (exact by construction), then switching one kernel / GEMM form on at a time and keeping it only if nothing
 changes.  A segment whose kernel does not reproduce torch on the installed stack (another libm, another hipBLASLt) silently stays on
 torch's ops; if even the all-torch form differs the caller keeps the module path.  The plan is what bench.py prints as `exact_plan`.
+The acceptance rule (reference run, two consecutive runs, the attention's direct comparison, the report) is exact_proof.py's, shared
+with the OPT family; this file holds the Llama family's arithmetic, its options and the order and variants they are tried in.
 """
 from __future__ import annotations
 
@@ -31,7 +33,9 @@ import torch
 import torch.nn.functional as F
 
 from . import ops, streamk
-from .fused_block import LLAMA_FAMILY, FusedLlamaBlock, _FusedBlockFn, _class_in
+from .exact_proof import ExactBlockMixin, Proof, attention_forward_same, bits_equal, key_block_candidates
+from .exact_proof import exact_attention_backward, exact_attention_forward  # noqa: F401  (this module's public names since round 6: tests and tools import them here)
+from .fused_block import LLAMA_FAMILY, FusedLlamaBlock, _class_in
 
 # segments that have a first-party kernel form (False = torch's own ops in a local autograd graph)
 STREAMK = -1        # plan value of a dw_* option: the library kernel's stream-K summation structure
@@ -53,64 +57,7 @@ FLAG_OPTS = ("swiglu_contract", "norm_rsqrt_f32", "attn_kb")
 # tries the guess first, then the others
 
 
-def _bits_equal(a: torch.Tensor, b: torch.Tensor) -> bool:
-    if a.shape != b.shape or a.dtype != b.dtype:
-        return False
-    it = {2: torch.int16, 4: torch.int32}[a.element_size()]
-    return bool(torch.equal(a.contiguous().view(it), b.contiguous().view(it)))
-
-
-def _count_diff(a: torch.Tensor, b: torch.Tensor) -> int:
-    """number of values whose bits differ (everything, when the shapes or dtypes do)"""
-    if a.shape != b.shape or a.dtype != b.dtype:
-        return int(max(a.numel(), b.numel()))
-    it = {2: torch.int16, 4: torch.int32}[a.element_size()]
-    return int((a.contiguous().view(it) != b.contiguous().view(it)).sum())
-
-
-def exact_attention_forward(q4, k4, v4, mask, scale, S, key_block=0):
-    """first-party attention with the library's bits (ops.attn_fwd_exact) when the call is one it takes: the calibration flow's
-    structured additive mask, head size 64 / 128, a sequence the backward kernels take too.  -> (q4, k4, v4, out [B, S, H, D], lse,
-    mask_struct) or None"""
-    if mask is None or S % 128 or S > 4096:
-        return None
-    st = ops.mask_structure(mask, S)
-    if st is None:
-        return None
-    kb = int(key_block) or ops.attn_key_block_guess(int(q4.shape[-1]), int(S))
-    got = ops.attn_fwd_exact(q4, k4, v4, st, float(scale), key_block=kb)
-    if got is None:
-        return None
-    return (q4, k4, v4, got[0], got[1], st)
-
-
-def exact_attention_backward(xa, dattn4, scale, outs=None):
-    """gradients of the call `exact_attention_forward` made: -> (gq4 [B, H, S, D], gk4, gv4 [B, H / kv_rep, S, D]) -- the kv_rep query
-    heads of a group summed as autograd's expand backward does (one fp32 sum per value, rounded once).
-    outs (kv_rep == 1 only): three [B * S, H * D] destinations (column slices of a merged gradient buffer) the kernels write into."""
-    q4, k4, v4, o4, lse, st = xa
-    B, H, S, D = q4.shape
-    hk = k4.shape[1]
-    kw = {}
-    if outs is not None and hk == H:
-        kw = dict(dq=outs[0], dk=outs[1], dv=outs[2])
-    got = ops.attn_bwd_exact(q4, k4, v4, o4, lse, dattn4, st, float(scale), **kw)
-    if got is None:
-        raise RuntimeError("ar_attn_bwd_exact refused a call whose forward it took")
-    dq, dke, dve = (t if t.dim() == 4 else t.view(B, S, H, D) for t in got)
-    gq4 = dq.transpose(1, 2)
-    if hk == H:
-        return gq4, dke.transpose(1, 2), dve.transpose(1, 2)
-    rep = H // hk
-    gk4 = dke.transpose(1, 2).reshape(B, hk, rep, S, D).sum(2)
-    gv4 = dve.transpose(1, 2).reshape(B, hk, rep, S, D).sum(2)
-    return gq4, gk4, gv4
-
-
-class ExactLlamaBlock(FusedLlamaBlock):
-    capturable = False          # the attention runs in a local autograd graph: the iteration is host-driven
-    exact = True
-
+class ExactLlamaBlock(ExactBlockMixin, FusedLlamaBlock):
     @classmethod
     def try_build(cls, block, arenas, input_others, amp_dtype=torch.bfloat16, sdpa_ctx=None, amp=True, **_) -> Optional["ExactLlamaBlock"]:
         if not _class_in(block, LLAMA_FAMILY):
@@ -126,13 +73,9 @@ class ExactLlamaBlock(FusedLlamaBlock):
         pe = (input_others or {}).get("position_embeddings")
         if any(t.dtype != self.dtype for t in pe):      # q * cos would promote: another rounding chain
             return None
-        self.amp = bool(amp)
-        self.plan: Dict[str, bool] = self.base_plan()
         self._tnx: Dict[str, torch.Tensor] = {}
         self._last_sk: Dict[str, Optional[list]] = {}
-        self.plan_report: Optional[dict] = None
-        self._attn_verify = False
-        self._attn_diffs: Dict[str, int] = {}
+        self._init_exact_state(amp)
         return self
 
     @classmethod
@@ -141,8 +84,6 @@ class ExactLlamaBlock(FusedLlamaBlock):
         and the quantised-output forward that feeds the next block (composer.py steps 3 and 6) through the same kernels -- their
         results enter the loss and the next block's input, so they must carry the module code's bits too
         (`plan_forward_against_module`).  Refused like the fused form (hooks on a projection, activation-quant shells)."""
-        import types
-
         if not _class_in(block, LLAMA_FAMILY):
             return None
         self = super().try_build_plain(block, input_others, amp_dtype, sdpa_ctx=sdpa_ctx)
@@ -157,15 +98,10 @@ class ExactLlamaBlock(FusedLlamaBlock):
         if any(t.dtype != self.dtype for t in pe):
             return None
         mods = dict(q=attn.q_proj, k=attn.k_proj, v=attn.v_proj, o=attn.o_proj, g=mlp.gate_proj, u=mlp.up_proj, d=mlp.down_proj)
-        self.layers = {n: types.SimpleNamespace(weight_q=m.weight, orig_layer=m) for n, m in mods.items()}
         self.arenas = []
-        self.amp = bool(amp)
-        self.plan = self.base_plan()
         self._tnx = {}
         self._last_sk = {}
-        self.plan_report = None
-        self._attn_verify = False
-        self._attn_diffs = {}
+        self._init_exact_state(amp, plain=mods)
         return self
 
     @staticmethod
@@ -184,13 +120,7 @@ class ExactLlamaBlock(FusedLlamaBlock):
         segment on torch's own ops, then one elementwise kernel at a time.  -> the plan (installed), or None (module path)."""
         with torch.no_grad():
             y_ref = module_forward(x, others).detach()
-
-            def same(plan):
-                self.set_plan(plan)
-                try:
-                    return _bits_equal(self._forward_impl(x, others, None).detach(), y_ref)
-                except (RuntimeError, ValueError, NotImplementedError):
-                    return False
+            same = lambda plan: self._forward_same(plan, x, others, y_ref)  # noqa: E731
 
             plan = self.base_plan()
             if not same(plan):
@@ -198,7 +128,7 @@ class ExactLlamaBlock(FusedLlamaBlock):
                 return None
             x2d = x.reshape(-1, x.shape[-1]).to(self.dtype).contiguous()
             res = ops.rmsnorm_fwd_exact(x2d, self.w1, self.eps1)
-            stats_ok = res is not None and _bits_equal(res[1], torch.rsqrt(x2d.float().pow(2).mean(-1, keepdim=True) + self.eps1).view(-1))
+            stats_ok = res is not None and bits_equal(res[1], torch.rsqrt(x2d.float().pow(2).mean(-1, keepdim=True) + self.eps1).view(-1))
             kept = []
             for opt in KERNEL_OPTS:
                 if opt in ("norm1", "norm2", "qknorm") and not stats_ok:
@@ -210,13 +140,9 @@ class ExactLlamaBlock(FusedLlamaBlock):
                     if others.get("attention_mask") is None:
                         continue
                     ok = False
-                    guess = ops.attn_key_block_guess(self.hd, int(x.shape[1]))
-                    for kb in [0] + [b for b in (64, 32, 16) if b != guess]:
+                    for kb in key_block_candidates(ops.attn_key_block_guess(self.hd, int(x.shape[1]))):
                         trial = dict(plan, attn=True, attn_kb=kb)
-                        self._attn_verify, self._attn_diffs = True, {}
-                        ok = same(trial)
-                        self._attn_verify = False
-                        ok = ok and self._attn_diffs.get("out", -1) == 0
+                        ok = attention_forward_same(self, same, trial, runs=1)
                         if ok:
                             break
                 else:
@@ -250,19 +176,6 @@ class ExactLlamaBlock(FusedLlamaBlock):
     def _refresh_tn(self):
         for key, wt in self._tnx.items():
             ops.transpose16(self.layers[key].weight_q, out=wt)
-
-    def _ctx(self, S):
-        """what the module path runs under: the quantizer's SDPA backend choice and (with amp) autocast"""
-        st = contextlib.ExitStack()
-        if self.sdpa_ctx is not None:
-            st.enter_context(self.sdpa_ctx(S))
-        if self.amp:
-            st.enter_context(torch.autocast(device_type=self.w1.device.type, dtype=self.dtype))
-        return st
-
-    def _bias(self, key):
-        b = self.layers[key].orig_layer.bias
-        return None if b is None else b.to(self.dtype)
 
     def _dw_x(self, key, dY2d, X2d):
         """dW of layer `key` (or of the merged "qkv" / "gu" slices) into the arena: the library GEMM exactly as _QLinearFn.backward
@@ -299,11 +212,7 @@ class ExactLlamaBlock(FusedLlamaBlock):
                 out2d.addmm_(dY2d.t(), X2d)
             else:
                 torch.mm(dY2d.t(), X2d, out=out2d)
-        for lyr in lyrs:
-            lyr._dw_accum[0] = True
-            post = getattr(lyr, "_post_dw", None)
-            if post is not None:
-                post()
+        self._dw_written(lyrs)
 
     def _streamk_found(self, key):
         """what the last `_dw_x(key, ...)` with plan value STREAMK really launched: per layer of `key` the stream-K structure found for
@@ -397,26 +306,8 @@ class ExactLlamaBlock(FusedLlamaBlock):
             rope_graph = (ql, kl, qr4, kr4)
             qr4, kr4 = qr4.detach(), kr4.detach()
         v4 = v2d.view(B, S, hkv, hd).transpose(1, 2)
-        # attention: transformers' own sdpa_attention_forward on the layouts the module hands over
-        from transformers.integrations.sdpa_attention import sdpa_attention_forward
-
-        mask = others.get("attention_mask")
-        xa = exact_attention_forward(qr4, kr4, v4, mask, self.attn.scaling, S, P.get("attn_kb", 0)) if P.get("attn") else None
-        al = ao = None
-        if xa is None and mask is not None and getattr(self, "materialise_mask_rows", False) and mask.shape[0] == 1 and B > 1:
-            mask = mask.expand(B, *mask.shape[1:]).contiguous()      # (the quantizer handed the shared mask over un-materialised)
-        if xa is None or self._attn_verify:
-            with torch.enable_grad() if grad else contextlib.nullcontext():
-                al = [t.detach().requires_grad_(grad) for t in (qr4, kr4, v4)]
-                with self._ctx(S):
-                    ao, _ = sdpa_attention_forward(self.attn, al[0], al[1], al[2], mask, dropout=0.0, scaling=self.attn.scaling)
-                    ao = ao.reshape(B, S, -1).contiguous()
-        if xa is not None:
-            if ao is not None:          # the proof: torch's attention output beside the first-party one
-                self._attn_diffs["out"] = self._attn_diffs.get("out", 0) + _count_diff(xa[3].view(B, S, -1), ao.detach())
-            a2d = xa[3].view(T, hq * hd)
-        else:
-            a2d = ao.detach().view(T, hq * hd)
+        # attention: transformers' own sdpa_attention_forward on the layouts the module hands over, or the first-party kernels
+        a2d, attn_saved = self._attention_forward(qr4, kr4, v4, others.get("attention_mask"), self.attn.scaling, grad)
         a_in = fq(a2d, aq["o"])
         o_out = F.linear(a_in, L["o"].weight_q, self._bias("o"))
         # residual + post_attention_layernorm
@@ -455,7 +346,7 @@ class ExactLlamaBlock(FusedLlamaBlock):
         d_out = F.linear(act_in, L["d"].weight_q, self._bias("d"))
         y = x2 + d_out
         if grad:
-            sv.update(B=B, S=S, h1_in=h1_in, cos=cos, sin=sin, rope_graph=rope_graph, qkn=qkn, attn_leaves=al, attn_out=ao, attn_x=xa, a2d=a2d, a_in=a_in,
+            sv.update(B=B, S=S, h1_in=h1_in, cos=cos, sin=sin, rope_graph=rope_graph, qkn=qkn, attn=attn_saved, a2d=a2d, a_in=a_in,
                       x2=x2, rstd2=rstd2, norm_graph=norm_graph, h2=h2, h2_in=h2_in, g2d=g2d, u2d=u2d, act_graph=act_graph, act=act,
                       act_in=act_in)
             ctx.saved = sv
@@ -519,15 +410,8 @@ class ExactLlamaBlock(FusedLlamaBlock):
         self._dw_x("o", dx2, s.pop("a_in"))
         da = bq(self._dx_x("o", dx2), s.pop("a2d"), aq["o"])
         del dx2
-        al, ao, xa = s.pop("attn_leaves"), s.pop("attn_out"), s.pop("attn_x")
-        if xa is not None:
-            gq4, gk4, gv4 = exact_attention_backward(xa, da.view(B, S, hq, hd), self.attn.scaling)
-            if ao is not None:          # the proof: torch's gradients beside the first-party ones
-                for name, mine, ref in zip(("dq", "dk", "dv"), (gq4, gk4, gv4), torch.autograd.grad(ao, al, da.view(B, S, hq * hd))):
-                    self._attn_diffs[name] = self._attn_diffs.get(name, 0) + _count_diff(mine, ref)
-        else:
-            gq4, gk4, gv4 = torch.autograd.grad(ao, al, da.view(B, S, hq * hd))
-        del al, ao, xa, da
+        gq4, gk4, gv4 = self._attention_backward(s.pop("attn"), da, B, S, self.attn.scaling)
+        del da
         rope_graph = s.pop("rope_graph")
         nq, nk = hq * hd, hkv * hd
         dqkv = torch.empty((T, nq + 2 * nk), dtype=self.dtype, device=dy2d.device) if P["dw_qkv"] else None
@@ -571,14 +455,6 @@ class ExactLlamaBlock(FusedLlamaBlock):
             self._dw_x("v", dv2d.contiguous(), h1_in)
 
     # -- the proof -----------------------------------------------------------------------------------------------------------
-    def _run_once(self, x, others, dpred):
-        for a in self.arenas:
-            for l in a.layers:
-                l._dw_accum[0] = False
-        y = _FusedBlockFn.apply(x, self.arena.token, self, others)
-        y.backward(dpred)
-        return y.detach(), [a.dWq.clone() for a in self.arenas]
-
     def plan_against_module(self, module_forward, x, others, ref, want=None, second=None) -> Optional[dict]:
         """One minibatch `x` ([rows, S, H], the loop's real minibatch shape: the library picks its GEMM kernels by shape) with targets
         `ref`: forward + loss gradient + backward through the module code (`module_forward(x, others)` -> prediction attached to
@@ -586,62 +462,18 @@ class ExactLlamaBlock(FusedLlamaBlock):
         all-torch form reproduces the module path's bits (the caller then keeps the module path).  `want`: options to try
         (default: every kernel and GEMM form).  `second` = (x, others, ref) of ANOTHER minibatch of the same shape.
 
-        Acceptance (round 5): an option joins the plan only after TWO CONSECUTIVE runs with nothing differing -- the
-        second one on the second minibatch when there is one -- so that a form that is only usually equal, or an intermittent
+        Acceptance (exact_proof.Proof; round 5): an option joins the plan only after TWO CONSECUTIVE runs with nothing
+        differing -- the second one on the second minibatch when there is one -- so that a form that is only usually equal, or an intermittent
         first-party defect, cannot pass as "1 of 2".  The library under the comparison is itself not perfectly repeatable (about one
         200-iteration digest run in sixty parts, profiles/r04_digest_repeat.json), so a non-GEMM option whose pair of runs failed gets
         ONE more pair; that, and every option that ends up dropped (with the number of differing values), is reported through
         `warnings.warn` and in `plan_report` -- a library bump must not cost 20 % silently."""
-        import warnings
-
-        for a in self.arenas:
-            if not a.wq_fresh:
-                a.qdq_forward()
-        reset = lambda: [l._dw_accum.__setitem__(0, False) for a in self.arenas for l in a.layers]  # noqa: E731
-
-        def module_reference(xb, ob, rb):
-            reset()
-            pred = module_forward(xb, ob)
-            pred_c = pred if pred.is_contiguous() else pred.contiguous()
-            dpred = torch.empty_like(pred_c)
-            scratch = torch.zeros(1, dtype=torch.float32, device=xb.device)
-            ops.mse_loss_fwd_bwd(pred_c, rb.to(pred_c.dtype), dpred=dpred, loss_accum=scratch, accum_scale=1.0, grad_scale=1000.0)
-            pred_c.backward(dpred)
-            return xb, ob, dpred, pred_c.detach(), [a.dWq.clone() for a in self.arenas]
-
-        mbs = [module_reference(x, others, ref)]
-        if second is not None:
-            mbs.append(module_reference(*second))
-        report = dict(errors={}, tried=[], kept=[], skipped={}, dropped={}, minibatches=len(mbs))
-
-        def mismatches(plan, mb=0) -> int:
-            """number of values of the block output and of every weight gradient that differ from the module path's (-1: the form
-            refused the shape)"""
-            xb, ob, dpred, y_ref, dw_ref = mbs[mb]
-            self.set_plan(plan)
-            try:
-                y, dws = self._run_once(xb, ob, dpred)
-            except (RuntimeError, ValueError, NotImplementedError) as e:      # a kernel refusing the shape: not an option here
-                report["errors"][",".join(k for k, v in plan.items() if v)] = repr(e)[:200]
-                return -1
-            return _count_diff(y, y_ref) + sum(_count_diff(a, b) for a, b in zip(dws, dw_ref))
-
-        def proven(plan):
-            """two consecutive runs without a differing value -> (True, 0), else (False, differing values of the run that failed)"""
-            n = mismatches(plan, 0)
-            if n != 0:
-                return False, n
-            n = mismatches(plan, len(mbs) - 1)
-            return n == 0, n
-
+        proof = Proof(self, module_forward, [(x, others, ref)] + ([second] if second is not None else []))
+        report, proven = proof.report, proof.proven
         plan = self.base_plan()
         ok, n_bad = proven(plan)
         if not ok:
-            reset()
-            self.plan_report = dict(report, usable=False, base_mismatches=n_bad)
-            warnings.warn(f"exact_rounding: even with every segment on torch's own ops {type(self.block).__name__} differs from the module "
-                          f"path ({n_bad} values); blocks of this kind keep the module path")
-            return None
+            return proof.refuse(n_bad)
 
         def norm_stats_match(rsqrt_f32):
             """the norm kernels' fp32 row statistics against torch's own ops on the probe minibatch: one bit of rstd rarely moves a
@@ -651,7 +483,7 @@ class ExactLlamaBlock(FusedLlamaBlock):
             if res is None:
                 return False
             want_r = torch.rsqrt(x2d.float().pow(2).mean(-1, keepdim=True) + self.eps1).view(-1)
-            return _bits_equal(res[1], want_r)
+            return bits_equal(res[1], want_r)
 
         def tiles(key):
             w = self.layers[key].weight_q
@@ -677,8 +509,7 @@ class ExactLlamaBlock(FusedLlamaBlock):
             if opt == "swiglu":
                 variants.append(dict(trial, swiglu_contract=False))
             if opt == "attn":       # the library picks its forward configuration by shape: the measured guess first, then the other key blocks
-                guess = ops.attn_key_block_guess(self.hd, int(x.shape[1]))
-                variants = [dict(trial, attn_kb=0)] + [dict(trial, attn_kb=kb) for kb in (64, 32, 16) if kb != guess]
+                variants = [dict(trial, attn_kb=kb) for kb in key_block_candidates(ops.attn_key_block_guess(self.hd, int(x.shape[1])))]
             if opt in ("norm1", "norm2") and not (plan["norm1"] or plan["norm2"]):
                 variants = [tv for tv in (trial, dict(trial, norm_rsqrt_f32=True)) if norm_stats_match(tv["norm_rsqrt_f32"])]
                 if not variants:
@@ -694,15 +525,7 @@ class ExactLlamaBlock(FusedLlamaBlock):
             worst = {}
             for attempt in (0, 1):
                 for vi, tv in enumerate(variants):
-                    if opt == "attn":           # torch's attention runs beside the kernels: outputs and gradients compared directly
-                        self._attn_verify, self._attn_diffs = True, {}
-                    ok, n_bad = proven(tv)
-                    if opt == "attn":
-                        self._attn_verify = False
-                        direct = dict(self._attn_diffs)
-                        report.setdefault("attn_direct", []).append(direct)
-                        if set(direct) != {"out", "dq", "dk", "dv"} or any(direct.values()):
-                            ok, n_bad = False, (n_bad if n_bad else sum(direct.values()) or -1)
+                    ok, n_bad = proof.proven_attention(tv) if opt == "attn" else proven(tv)
                     if not ok:
                         worst[str(tv.get(opt)) if opt.startswith("dw_") else str(vi)] = n_bad
                         continue
@@ -717,18 +540,10 @@ class ExactLlamaBlock(FusedLlamaBlock):
                     plan = tv
                     report["kept"].append(opt)
                     if attempt:
-                        report.setdefault("kept_on_second_try", []).append(opt)
-                        warnings.warn(f"exact_rounding: option {opt} differed from the module path in its first pair of runs ({worst}) and "
-                                      f"matched in the second pair -- kept; the library under the comparison is not perfectly repeatable")
+                        proof.kept_on_second_try(opt, worst)
                     break
                 if opt in report["kept"] or opt.startswith("dw_"):
                     break
             if opt not in report["kept"]:
                 report["dropped"][opt] = worst
-        if report["dropped"]:
-            warnings.warn(f"exact_rounding: {type(self.block).__name__}: not bit-equal to the module path on this stack and left on the "
-                          f"module path's own form (slower): {report['dropped']} (differing values per tried form)")
-        self.set_plan(plan)
-        reset()
-        self.plan_report = dict(report, usable=True, plan={k: (int(v) if (k.startswith("dw_") or k == "attn_kb") else bool(v)) for k, v in plan.items()})
-        return plan
+        return proof.finish(plan, is_int=lambda k: k.startswith("dw_") or k == "attn_kb", left_on="the module path's own form", per="form")

@@ -692,7 +692,7 @@ def attn_key_block_guess(head_dim: int, seq: int) -> int:
 def attn_fwd_exact(q4: torch.Tensor, k4: torch.Tensor, v4: torch.Tensor, mask_struct, scale: float, key_block: int = 0):
     """The attention forward with the LIBRARY'S bits (ar_attn_fwd_exact, csrc/ar_attn_exact.hip): what
     `F.scaled_dot_product_attention(q4, repeat_kv(k4), repeat_kv(v4), attn_mask=<the structured 0 / 1 mask>, scale=scale)` returns on
-    this stack, value for value -- callers PROVE that per call signature before relying on it (exact_block.plan_against_module).
+    this stack, value for value -- callers PROVE that per call signature before relying on it (exact_proof.Proof.proven_attention).
     q4 [B, H, S, D], k4 / v4 [B, H / kv_rep, S, D]: bf16 views with unit stride along D (token-major or head-major).
     mask_struct = (bias_in, bias_out, valid_len) from `mask_structure`.  key_block: keys per online-softmax step (0 = the tuning
     minibatch's; 16 / 32 / 64: the library's other configurations, see the header).  -> (out [B, S, H, D] contiguous, lse [B, H, S] fp32), or

@@ -307,7 +307,7 @@ class SignRoundConfig:
     # Llama-family blocks through first-party kernels that keep the MODULE PATH'S BITS (auto_round_amd/exact_block.py,
     # csrc/ar_exact.hip): eager torch's rounding points and reduction order in the elementwise kernels, the module path's GEMM
     # shapes plus whichever faster GEMM forms prove bit-equal on this GPU / software stack.  Verified against the module code on
-    # one real minibatch per kind of block before it is used; where the proof fails the module path runs.  Takes precedence over
+    # one real minibatch per kind of block before it is used (auto_round_amd/exact_proof.py); where the proof fails the module path runs.  Takes precedence over
     # `fused_block` (whose rounding points differ): with this switch on a block is never tuned on a path that is not bit-identical
     # to the module path.  The proof is a one-off cost per kind of block (classes, every linear's shape and dtype, minibatch shape,
     # mask): about 50 forward + backward passes with clones of the weight gradients -- ~1.5 s at Llama-3-8B's block dimensions, ~10 s
@@ -782,7 +782,7 @@ class SignRoundQuantizer:
         import warnings
 
         from . import attention as A
-        from .exact_block import _count_diff
+        from .exact_proof import attn_direct_ok, reference_run, reset_dw_accum, run_diff
 
         mask = input_others.get("attention_mask") if isinstance(input_others, dict) else None
         cfgs = {}
@@ -811,18 +811,11 @@ class SignRoundQuantizer:
         for a in arenas:
             if not a.wq_fresh:
                 a.qdq_forward()
-        reset = lambda: [l._dw_accum.__setitem__(0, False) for a in arenas for l in a.layers]  # noqa: E731
 
         def run(lo):
-            reset()
-            xb = X[lo:lo + rows].clone()
-            pred = self.block_forward(block, xb, input_others)
-            pred_c = pred if pred.is_contiguous() else pred.contiguous()
-            dpred = torch.empty_like(pred_c)
-            scratch = torch.zeros(1, dtype=torch.float32, device=xb.device)
-            ops.mse_loss_fwd_bwd(pred_c, Y[lo:lo + rows].to(pred_c.dtype), dpred=dpred, loss_accum=scratch, accum_scale=1.0, grad_scale=1000.0)
-            pred_c.backward(dpred)
-            return pred_c.detach(), [a.dWq.clone() for a in arenas]
+            _, y, dws = reference_run(lambda x, o: self.block_forward(block, x, o), arenas, X[lo:lo + rows].clone(), input_others,
+                                      Y[lo:lo + rows])
+            return y, dws
 
         los = [0] + ([rows] if X.shape[0] >= 2 * rows else [])
         report = dict(minibatches=len(los))
@@ -837,12 +830,11 @@ class SignRoundQuantizer:
                 n_bad = 0
                 for lo, (y_ref, dw_ref) in zip(los, refs):
                     y, dws = run(lo)
-                    n_bad += _count_diff(y, y_ref) + sum(_count_diff(a, b) for a, b in zip(dws, dw_ref))
+                    n_bad += run_diff(y, dws, y_ref, dw_ref)
                 direct = dict(A.exact_state["diffs"])
                 report.update(block_mismatches=n_bad, attn_direct=direct, calls=A.exact_state["calls"], fallbacks=A.exact_state["fallbacks"],
                               key_block=kb)
-                if (n_bad == 0 and A.exact_state["calls"] > 0 and A.exact_state["fallbacks"] == 0
-                        and set(direct) == {"out", "dq", "dk", "dv"} and not any(direct.values())):
+                if n_bad == 0 and A.exact_state["calls"] > 0 and A.exact_state["fallbacks"] == 0 and attn_direct_ok(direct):
                     verdict = kb if kb else True
                     break
                 if A.exact_state["calls"] == 0:      # no call the kernels take: other key blocks will not change that
@@ -852,7 +844,7 @@ class SignRoundQuantizer:
             verdict = False
         finally:
             A.exact_state["verify"] = False
-            reset()
+            reset_dw_accum(arenas)
         self._modattn_verdict[key] = verdict
         self.last_module_attention_report = dict(report, usable=bool(verdict))
         if not verdict:
@@ -866,6 +858,7 @@ class SignRoundQuantizer:
         later blocks of the same kind reuse the plan."""
         from .exact_block import ExactLlamaBlock
         from .exact_opt_block import ExactOPTBlock
+        from .exact_proof import reset_dw_accum
 
         cfg = self.config
         if cfg.data_parallel or not isinstance(input_others, dict):
@@ -887,7 +880,7 @@ class SignRoundQuantizer:
                 o = input_others if not per_sample_others else {**input_others, **{k: t[lo:lo + rows] for k, t in per_sample_others.items()}}
                 return self._others_for(rows, o)
 
-            # a second minibatch of the same shape for the confirming run of every option (exact_block.plan_against_module)
+            # a second minibatch of the same shape for the confirming run of every option (exact_proof.Proof.proven)
             second = (X[rows:2 * rows].clone(), others_of(rows), Y[rows:2 * rows]) if X.shape[0] >= 2 * rows else None
             try:
                 plan = eb.plan_against_module(lambda x, o: self.block_forward(block, x, o), X[:rows].clone(), others_of(0), Y[:rows],
@@ -897,9 +890,7 @@ class SignRoundQuantizer:
 
                 warnings.warn(f"exact_rounding: the proof against the module code raised {e!r}; {type(block).__name__} keeps the module path")
                 plan = None
-                for a in arenas:
-                    for l in a.layers:
-                        l._dw_accum[0] = False
+                reset_dw_accum(arenas)
             self._exact_plans[key] = plan if plan is not None else False
             self.last_exact_report = eb.plan_report
         if not plan:
