@@ -272,14 +272,12 @@ template <int DT> __device__ __forceinline__ void pin_raw(Raw8<DT>& r) {
         asm volatile("" : "+v"(r.q.x), "+v"(r.q.y), "+v"(r.q.z), "+v"(r.q.w));
 }
 
-#ifndef AR_ACT_WAVES
-#define AR_ACT_WAVES 1
-#endif
+constexpr int kActWavesPerEu = 1;   // amdgpu_waves_per_eu of the lane-group kernels
 // ---- lane-group kernels ----------------------------------------------------------------------------------------------
 // A lane owns CH consecutive 16-byte chunks (8 * CH elements) of its group; the backward takes CH = 2 where the group size
 // allows it, which halves the per-lane share of the group arithmetic (range, scale, routing, butterflies).
 template <int ADT, int XR, bool BWD, int CPG, bool SYM, int CH>
-__global__ __launch_bounds__(kTPB) __attribute__((amdgpu_waves_per_eu(AR_ACT_WAVES))) void k_int_act(const void* __restrict__ dXq, const void* __restrict__ X,
+__global__ __launch_bounds__(kTPB) __attribute__((amdgpu_waves_per_eu(kActWavesPerEu))) void k_int_act(const void* __restrict__ dXq, const void* __restrict__ X,
                                                   void* __restrict__ Out, void* __restrict__ scale_out, int64_t n_groups,
                                                   int bits, int s_dt, float thresh) {
     constexpr int cpg = CPG;        // lanes per group: compile-time, so the butterflies are fixed DPP controls
@@ -384,9 +382,7 @@ __global__ __launch_bounds__(kTPB) __attribute__((amdgpu_waves_per_eu(AR_ACT_WAV
 // back for the later passes, so X is read from memory once.  A thread only ever re-reads its own pieces: LDS is a per-thread
 // extension of the register file here and needs no barrier; the team reduces through DPP / ds_bpermute inside a wave and one
 // small LDS exchange across waves.  (Keeping the pieces in registers instead unrolls every pass over them: 250+ VGPRs.)
-#ifndef AR_ACT_ROW_WAVE_MAX
-#define AR_ACT_ROW_WAVE_MAX 512     // chunks (of 8 elements) up to which one wave owns a group (4096 elements)
-#endif
+constexpr int kActRowWaveMax = 512;     // chunks (of 8 elements) up to which one wave owns a group (4096 elements)
 template <int WAVES> struct TeamLds { float f[2][6][4]; };
 // all-reduce of N values across the waves of a team (each already reduced inside its wave): one LDS exchange, one barrier
 template <int WAVES, int N, class F>
@@ -617,7 +613,7 @@ static int launch_int_act(const void* dXq, const void* X, void* Out, void* scale
         const size_t row_bytes = (size_t)c8 * (a_dt == AR_DT_F32 ? 32 : 16);
         // measured at 4096-element groups: forward 5.7 TB/s with the workgroup as the team against 5.1 with a wave, backward 3.9
         // against 4.9 -- so the forward switches to the workgroup as soon as every thread has a chunk
-        row_waves = (c8 <= (BWD ? AR_ACT_ROW_WAVE_MAX : 255)) ? 1 : 4;
+        row_waves = (c8 <= (BWD ? kActRowWaveMax : 255)) ? 1 : 4;
         row_lds_bytes = row_bytes * (kTPB / (kWave * row_waves));
         if (row_lds_bytes + 512 > 65536 && row_waves == 1) { row_waves = 4; row_lds_bytes = row_bytes; }
         if (row_lds_bytes + 512 > 65536) row_waves = 0;
@@ -626,46 +622,31 @@ static int launch_int_act(const void* dXq, const void* X, void* Out, void* scale
     const int64_t teams_per_block = row_nc ? kTPB / (kWave * row_waves) : kTPB / kWave;
     const int64_t want = lane_groups ? (n_groups * cpg + kTPB - 1) / kTPB : (n_groups + teams_per_block - 1) / teams_per_block;
     const int grid = (int)(want < 1 ? 1 : (want > (1 << 22) ? (1 << 22) : want));
-#define AR_ACT_ROW(ADT, XR, W)                                                                                               \
-    hipLaunchKernelGGL((k_int_act_row<ADT, XR, BWD, SYM, W>), grid, kTPB, row_lds_bytes, st, dXq, X, Out, scale_out, n_groups, \
-                       gs / kEPT, bits, s_dt, q_thresh)
-#define AR_ACT_LG(ADT, XR, C)                                                                                                \
-    do {                                                                                                                     \
-        if constexpr (BWD) {                                                                                                 \
-            if (two) hipLaunchKernelGGL((k_int_act<ADT, XR, BWD, C, SYM, 2>), grid, kTPB, 0, st, dXq, X, Out, scale_out,     \
-                                        n_groups, bits, s_dt, q_thresh);                                                     \
-            else hipLaunchKernelGGL((k_int_act<ADT, XR, BWD, C, SYM, 1>), grid, kTPB, 0, st, dXq, X, Out, scale_out,         \
-                                    n_groups, bits, s_dt, q_thresh);                                                         \
-        } else hipLaunchKernelGGL((k_int_act<ADT, XR, BWD, C, SYM, 1>), grid, kTPB, 0, st, dXq, X, Out, scale_out, n_groups, \
-                                  bits, s_dt, q_thresh);                                                                     \
-    } while (0)
-#define AR_ACT(ADT, XR)                                                                                                      \
-    do {                                                                                                                     \
-        if (lane_groups) {                                                                                                   \
-            switch (cpg) {                                                                                                   \
-                case 1: AR_ACT_LG(ADT, XR, 1); break;                                                                        \
-                case 2: AR_ACT_LG(ADT, XR, 2); break;                                                                        \
-                case 4: AR_ACT_LG(ADT, XR, 4); break;                                                                        \
-                case 8: AR_ACT_LG(ADT, XR, 8); break;                                                                        \
-                case 16: AR_ACT_LG(ADT, XR, 16); break;                                                                      \
-                case 32: AR_ACT_LG(ADT, XR, 32); break;                                                                      \
-                default: AR_ACT_LG(ADT, XR, 64); break;                                                                      \
-            }                                                                                                                \
-        } else if (row_waves == 1) AR_ACT_ROW(ADT, XR, 1);                                                                   \
-        else if (row_waves == 4) AR_ACT_ROW(ADT, XR, 4);                                                                     \
-        else hipLaunchKernelGGL((k_int_act_wave<ADT, XR, BWD, SYM>), grid, kTPB, 0, st, dXq, X, Out, scale_out, n_groups,     \
-                                  gs / kEPT, bits, s_dt, q_thresh);                                                          \
-    } while (0)
-    switch (a_dt) {
-        case AR_DT_BF16: if (same16) AR_ACT(AR_DT_BF16, AR_DT_BF16); else AR_ACT(AR_DT_BF16, AR_DT_F32); break;
-        case AR_DT_F16: if (same16) AR_ACT(AR_DT_F16, AR_DT_F16); else AR_ACT(AR_DT_F16, AR_DT_F32); break;
-        case AR_DT_F32: AR_ACT(AR_DT_F32, AR_DT_F32); break;
-        default: return AR_ERR_UNSUPPORTED;
-    }
-#undef AR_ACT
+    // one lane-group width (CH = BWD ? 2 : 1: the forward has no two-chunk instantiation)
+#define AR_ACT_LG(C)                                                                                                           \
+    case C:                                                                                                                    \
+        if (BWD && two) hipLaunchKernelGGL((k_int_act<ADT, XR, BWD, C, SYM, BWD ? 2 : 1>), grid, kTPB, 0, st, dXq, X, Out, scale_out, \
+                                           n_groups, bits, s_dt, q_thresh);                                                    \
+        else hipLaunchKernelGGL((k_int_act<ADT, XR, BWD, C, SYM, 1>), grid, kTPB, 0, st, dXq, X, Out, scale_out, n_groups, bits, s_dt, \
+                                q_thresh);                                                                                     \
+        break
+    const bool known = dispatch_dt_pair(a_dt, same16, [&](auto at, auto xt) {
+        constexpr int ADT = decltype(at)::value, XR = decltype(xt)::value;
+        if (lane_groups) {
+            switch (cpg) { AR_ACT_LG(1); AR_ACT_LG(2); AR_ACT_LG(4); AR_ACT_LG(8); AR_ACT_LG(16); AR_ACT_LG(32); AR_ACT_LG(64); }
+        } else if (row_waves == 1) {
+            hipLaunchKernelGGL((k_int_act_row<ADT, XR, BWD, SYM, 1>), grid, kTPB, row_lds_bytes, st, dXq, X, Out, scale_out, n_groups,
+                               gs / kEPT, bits, s_dt, q_thresh);
+        } else if (row_waves == 4) {
+            hipLaunchKernelGGL((k_int_act_row<ADT, XR, BWD, SYM, 4>), grid, kTPB, row_lds_bytes, st, dXq, X, Out, scale_out, n_groups,
+                               gs / kEPT, bits, s_dt, q_thresh);
+        } else {
+            hipLaunchKernelGGL((k_int_act_wave<ADT, XR, BWD, SYM>), grid, kTPB, 0, st, dXq, X, Out, scale_out, n_groups, gs / kEPT, bits,
+                               s_dt, q_thresh);
+        }
+    });
 #undef AR_ACT_LG
-#undef AR_ACT_ROW
-    return launch_status();
+    return known ? launch_status() : AR_ERR_UNSUPPORTED;
 }
 
 extern "C" int ar_qdq_int_act_fwd(const void* X, void* Xq, void* scale_out, int64_t n_groups, int gs, int bits, int sym,

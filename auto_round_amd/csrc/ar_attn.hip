@@ -172,13 +172,10 @@ __global__ __launch_bounds__(64 * WAVES, 2) void k_attn_fwd(AttnArgs a) {
         for (int r = 0; r < 16; ++r) o[dt][r] = 0.f;
     float m_run = -INFINITY, l_run = 0.f;
 
-#ifndef AR_ATTN_ABL
-#define AR_ATTN_ABL 0      // timing experiments only (wrong results): 1 no K/V staging after the first tile, 2 no softmax arithmetic
-#endif
 #define AR_PINA() __builtin_amdgcn_sched_barrier(0)
-#define AR_KREAD(KS, T) if (!(AR_ATTN_ABL & 4)) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=&v"(kf[(KS) & 3][T]) : "v"(kA[KS]), "n"(BUF * ABUF + (T) * 32 * AROW) : "memory")
+#define AR_KREAD(KS, T) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=&v"(kf[(KS) & 3][T]) : "v"(kA[KS]), "n"(BUF * ABUF + (T) * 32 * AROW) : "memory")
 #define AR_VREAD(ST)                                                                                                     \
-    _Pragma("unroll") for (int dt = 0; dt < ND; ++dt) if (!(AR_ATTN_ABL & 4))                                            \
+    _Pragma("unroll") for (int dt = 0; dt < ND; ++dt)                                                                    \
         asm volatile("ds_read_b64_tr_b16 %0, %2 offset:%4\n\tds_read_b64_tr_b16 %1, %3 offset:%4"                        \
                      : "=&v"(vlo[(ST) & 1][dt]), "=&v"(vhi[(ST) & 1][dt])                                                \
                      : "v"(vAlo[dt]), "v"(vAhi[dt]), "n"(BUF * ABUF + ATILE + (ST) * 16 * AROW) : "memory");
@@ -204,10 +201,8 @@ __global__ __launch_bounds__(64 * WAVES, 2) void k_attn_fwd(AttnArgs a) {
             else if (ahead == 2) asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(kf[ks & 3][0]), "+v"(kf[ks & 3][1])::"memory");
             else if (ahead == 1) asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(kf[ks & 3][0]), "+v"(kf[ks & 3][1])::"memory");
             else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(kf[ks & 3][0]), "+v"(kf[ks & 3][1])::"memory");
-            if (!(AR_ATTN_ABL & 8)) {
             s[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(abf16x8_t, kf[ks & 3][0]), qf[ks], s[0], 0, 0, 0);
             s[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(abf16x8_t, kf[ks & 3][1]), qf[ks], s[1], 0, 0, 0);
-            }
             AR_PINA();
         }
         // the V^T fragments of the first 32 keys do not depend on the softmax: their reads fly under it
@@ -217,7 +212,6 @@ __global__ __launch_bounds__(64 * WAVES, 2) void k_attn_fwd(AttnArgs a) {
         AR_PINA();
         // ---- online softmax on the lane's query (column)
         const bool diag = k0 + AK - 1 > q0 + 32 * wave;                   // wave-uniform: the tile reaches past some query
-        if (!(AR_ATTN_ABL & 2)) {
         // row maximum on the raw scores (the scale is positive), then p = exp2(s * scale - m) as one fma + v_exp_f32
         float mx = -INFINITY;
         if (MASKED) {
@@ -269,7 +263,6 @@ __global__ __launch_bounds__(64 * WAVES, 2) void k_attn_fwd(AttnArgs a) {
                     o[dt][r] = v.x; o[dt][r + 1] = v.y;
                 }
         }
-        }
         AR_PINA();
         // ---- O^T += V^T P^T: 4 k-steps of 16 keys (sub-tile t, half s2) x ND d-tiles; two steps of fragments in flight
 #pragma unroll
@@ -301,8 +294,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void k_attn_fwd(AttnArgs a) {
 #pragma unroll
             for (int dt = 0; dt < ND; ++dt) {
                 const as16x8_t va = __builtin_shufflevector(vlo[st & 1][dt], vhi[st & 1][dt], 0, 1, 2, 3, 4, 5, 6, 7);
-                if (!(AR_ATTN_ABL & 8)) o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(abf16x8_t, va), __builtin_bit_cast(abf16x8_t, pb),
-                                                                o[dt], 0, 0, 0);
+                o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(abf16x8_t, va), __builtin_bit_cast(abf16x8_t, pb), o[dt], 0, 0, 0);
             }
             AR_PINA();
             if (st + 2 < 4) { AR_VREAD(st + 2) }
@@ -314,11 +306,11 @@ __global__ __launch_bounds__(64 * WAVES, 2) void k_attn_fwd(AttnArgs a) {
     for (int kt = 0; kt < n_kt; kt += 2) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();                                     // tile kt landed for everybody; buffer 1 is free
-        if (!(AR_ATTN_ABL & 1)) issue_tile(kt + 1, 1);
+        issue_tile(kt + 1, 1);
         if (MASKED || kt * AK <= q0 + 32 * wave + 31) tile(std::integral_constant<int, 0>{}, kt);     // else every query precedes the tile
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
-        if (kt + 2 < n_kt && !(AR_ATTN_ABL & 1)) issue_tile(kt + 2, 0);
+        if (kt + 2 < n_kt) issue_tile(kt + 2, 0);
         if (MASKED || (kt + 1) * AK <= q0 + 32 * wave + 31) tile(std::integral_constant<int, 1>{}, kt + 1);
     }
 #undef AR_KREAD

@@ -5,6 +5,8 @@
 #include <hip/hip_ext.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "ar_mi355x.h"
 
 namespace ar {
@@ -43,18 +45,11 @@ __device__ __forceinline__ uint32_t f32_to_f16(float f) {
 }
 // two fp32 -> packed bf16x2 with the gfx950 conversion instruction (v_cvt_pk_bf16_f32: RNE, NaN quieted); verified
 // against the integer RNE formula over all 2^32 inputs by tools/exactcheck (profiles/archive/r01_exactcheck.json).
-#ifndef AR_HW_BF16
-#define AR_HW_BF16 1
-#endif
 typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
 typedef float f32x2_t __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {
-#if AR_HW_BF16
     f32x2_t v; v.x = lo; v.y = hi;
     return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2_t));
-#else
-    return f32_to_bf16(lo) | (f32_to_bf16(hi) << 16);
-#endif
 }
 
 template <int DT> __device__ __forceinline__ float round_to(float v) {
@@ -94,46 +89,22 @@ template <> struct Raw8<AR_DT_BF16> { uint4 q; };
 template <> struct Raw8<AR_DT_F16> { uint4 q; };
 template <> struct Raw8<AR_DT_F32> { float4 a, b; };
 
-// 16-byte global accesses.  AR_NT=1 would mark the streaming arrays non-temporal.  Measured on MI355X (round 1, A/B in one
-// session, Llama-3-8B block): no gain for these kernels (fwd 5.0-5.2 TB/s either way), and with ROCm 7.2 the
-// __builtin_nontemporal_store path lost the sign of a -0 in the high fp16 half of the 4th dword (caught by the f16
-// golden test), so it stays off.
-#ifndef AR_NT
-#define AR_NT 0
-#endif
+// 16-byte global accesses, plain.  Marking the streaming arrays non-temporal (__builtin_nontemporal_load / _store) was measured on
+// MI355X (round 1, A/B in one session, Llama-3-8B block): no gain for these kernels (fwd 5.0-5.2 TB/s either way), and with ROCm 7.2
+// the non-temporal store lost the sign of a -0 in the high fp16 half of the 4th dword (caught by the f16 golden test).
 typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ uint4 ld16(const void* p) {
-#if AR_NT
-    const u32x4_t v = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(p));
-    return make_uint4(v.x, v.y, v.z, v.w);
-#else
     return *reinterpret_cast<const uint4*>(p);
-#endif
 }
 __device__ __forceinline__ float4 ld16f(const void* p) {
-#if AR_NT
-    const f32x4_t v = __builtin_nontemporal_load(reinterpret_cast<const f32x4_t*>(p));
-    return make_float4(v.x, v.y, v.z, v.w);
-#else
     return *reinterpret_cast<const float4*>(p);
-#endif
 }
 __device__ __forceinline__ void st16(void* p, uint4 q) {
-#if AR_NT
-    u32x4_t v; v.x = q.x; v.y = q.y; v.z = q.z; v.w = q.w;
-    __builtin_nontemporal_store(v, reinterpret_cast<u32x4_t*>(p));
-#else
     *reinterpret_cast<uint4*>(p) = q;
-#endif
 }
 __device__ __forceinline__ void st16f(void* p, float4 q) {
-#if AR_NT
-    f32x4_t v; v.x = q.x; v.y = q.y; v.z = q.z; v.w = q.w;
-    __builtin_nontemporal_store(v, reinterpret_cast<f32x4_t*>(p));
-#else
     *reinterpret_cast<float4*>(p) = q;
-#endif
 }
 template <int DT> __device__ __forceinline__ Raw8<DT> load8_raw(const void* base, int64_t elem) {
     Raw8<DT> r;
@@ -164,9 +135,6 @@ template <int DT> __device__ __forceinline__ void unpack8(const Raw8<DT>& r, flo
 // enumerates ALL bf16/fp16 weights x ALL admissible fp16 scales (2^32 pairs each, both for w/s and for (w/s)/s) and
 // finds bit-identical results to the IEEE division whenever |w| is in [2^-64, 2^64] or w == 0; outside that window the
 // kernels take the plain IEEE division (wave-uniform branch, never taken for real checkpoints).
-#ifndef AR_FASTDIV
-#define AR_FASTDIV 1
-#endif
 __device__ __forceinline__ bool div_fast_ok(float w) {
     const uint32_t e = (__float_as_uint(w) >> 23) & 0xffu;
     return (e - 63u <= 128u) || (w == 0.f);
@@ -352,6 +320,29 @@ __device__ __forceinline__ void group_scale(const IntCfg& c, float wmin, float w
 
 // error plumbing for the C ABI
 inline int launch_status() { return (int)hipGetLastError(); }
+
+// ---- run-time dtype code -> compile-time template argument (host) ------------------------------------------------------
+// f is a generic lambda that holds the launch; it is called with one tag per dtype (decltype(tag)::value is the AR_DT_* code).
+// Both return false for an unknown code and launch nothing.
+template <int V> using Int = std::integral_constant<int, V>;
+template <class F> inline bool dispatch_dt(int dt, F&& f) {
+    switch (dt) {
+        case AR_DT_BF16: f(Int<AR_DT_BF16>{}); return true;
+        case AR_DT_F16: f(Int<AR_DT_F16>{}); return true;
+        case AR_DT_F32: f(Int<AR_DT_F32>{}); return true;
+        default: return false;
+    }
+}
+// (storage dtype, evaluation dtype): torch evaluates tensor / scale in the promoted dtype -- the 16-bit type itself when both share it
+// (same16), fp32 otherwise.  Five pairs: (bf16, bf16), (bf16, f32), (f16, f16), (f16, f32), (f32, f32).
+template <class F> inline bool dispatch_dt_pair(int dt, bool same16, F&& f) {
+    switch (dt) {
+        case AR_DT_BF16: same16 ? f(Int<AR_DT_BF16>{}, Int<AR_DT_BF16>{}) : f(Int<AR_DT_BF16>{}, Int<AR_DT_F32>{}); return true;
+        case AR_DT_F16: same16 ? f(Int<AR_DT_F16>{}, Int<AR_DT_F16>{}) : f(Int<AR_DT_F16>{}, Int<AR_DT_F32>{}); return true;
+        case AR_DT_F32: f(Int<AR_DT_F32>{}, Int<AR_DT_F32>{}); return true;
+        default: return false;
+    }
+}
 
 // ---- optional per-launch device timing of the hot kernels (ar_profile_*, csrc/ar_prof.hip) ---------------------------
 // When profiling is on, a hot launch goes through hipExtLaunchKernelGGL with a start/stop event pair: the events carry the

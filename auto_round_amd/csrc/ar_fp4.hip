@@ -104,18 +104,11 @@ __device__ __forceinline__ void fp4_group_scale(int mode, float amax, float Ms, 
     }
 }
 
-#ifndef AR_FP4_FWD_UNROLL
-#define AR_FP4_FWD_UNROLL 1
-#endif
-#ifndef AR_FP4_BWD_UNROLL
-#define AR_FP4_BWD_UNROLL 2
-#endif
-#ifndef AR_FP4_ACT_UNROLL          // chunks per lane of the activation forward (4 B/elem: less HBM time to hide the math)
-#define AR_FP4_ACT_UNROLL 2
-#endif
-#ifndef AR_FP4_ABWD_UNROLL
-#define AR_FP4_ABWD_UNROLL 1
-#endif
+// chunks per lane in flight
+constexpr int kFp4FwdUnroll = 1;
+constexpr int kFp4BwdUnroll = 2;
+constexpr int kFp4ActUnroll = 2;    // the activation forward (4 B/elem: less HBM time to hide the math)
+constexpr int kFp4ActBwdUnroll = 1;
 
 // MODE (0 MXFP4 / 1 NVFP4) and ACT (dynamic activation fake-quant: no V / absmax / max_scale / init scale) are template
 // parameters: the group width (4 or 2 lanes) and every mode branch fold at compile time, the butterflies become fixed
@@ -275,27 +268,20 @@ extern "C" int ar_qdq_fp4_fwd(const void* X, const float* V, const float* absmax
     a.init_dev = init_scale_dev;
     a.n_groups = n_groups; a.cpg = gs / kEPT; a.mode = mode; a.init_scale = init_scale; a.lo = lo_bound; a.hi = hi_bound;
     const bool act = !V && !absmax && !max_s && !init_scale_dev && init_scale == 1.0f;
-    const int unroll = act ? AR_FP4_ACT_UNROLL : AR_FP4_FWD_UNROLL;
+    const int unroll = act ? kFp4ActUnroll : kFp4FwdUnroll;
     const int grid = fp4_grid((n_groups * a.cpg + unroll - 1) / unroll);
     hipStream_t st = (hipStream_t)stream;
-#define AR_FWD(DT)                                                                                                   \
-    do {                                                                                                             \
-        if (mode == 0) {                                                                                             \
-            if (act) hipLaunchKernelGGL((k_fp4_fwd<DT, AR_FP4_ACT_UNROLL, 0, true>), grid, kTPB, 0, st, a);          \
-            else AR_LAUNCH_PROF(AR_PROF_FP4_FWD, n_groups, (k_fp4_fwd<DT, AR_FP4_FWD_UNROLL, 0, false>), grid, kTPB, 0, st, a); \
-        } else {                                                                                                     \
-            if (act) hipLaunchKernelGGL((k_fp4_fwd<DT, AR_FP4_ACT_UNROLL, 1, true>), grid, kTPB, 0, st, a);          \
-            else AR_LAUNCH_PROF(AR_PROF_FP4_FWD, n_groups, (k_fp4_fwd<DT, AR_FP4_FWD_UNROLL, 1, false>), grid, kTPB, 0, st, a); \
-        }                                                                                                            \
-    } while (0)
-    switch (x_dt) {
-        case AR_DT_BF16: AR_FWD(AR_DT_BF16); break;
-        case AR_DT_F16: AR_FWD(AR_DT_F16); break;
-        case AR_DT_F32: AR_FWD(AR_DT_F32); break;
-        default: return AR_ERR_UNSUPPORTED;
-    }
-#undef AR_FWD
-    return launch_status();
+    const bool known = dispatch_dt(x_dt, [&](auto xt) {
+        constexpr int DT = decltype(xt)::value;
+        if (mode == 0) {
+            if (act) hipLaunchKernelGGL((k_fp4_fwd<DT, kFp4ActUnroll, 0, true>), grid, kTPB, 0, st, a);
+            else AR_LAUNCH_PROF(AR_PROF_FP4_FWD, n_groups, (k_fp4_fwd<DT, kFp4FwdUnroll, 0, false>), grid, kTPB, 0, st, a);
+        } else {
+            if (act) hipLaunchKernelGGL((k_fp4_fwd<DT, kFp4ActUnroll, 1, true>), grid, kTPB, 0, st, a);
+            else AR_LAUNCH_PROF(AR_PROF_FP4_FWD, n_groups, (k_fp4_fwd<DT, kFp4FwdUnroll, 1, false>), grid, kTPB, 0, st, a);
+        }
+    });
+    return known ? launch_status() : AR_ERR_UNSUPPORTED;
 }
 
 extern "C" int ar_pack_fp4(const void* Wq, const void* scale, const float* global_scale_dev, int64_t out_f, int64_t in_f,
@@ -305,7 +291,7 @@ extern "C" int ar_pack_fp4(const void* Wq, const void* scale, const float* globa
     if (n == 0) return AR_OK;
     const int grid = fp4_grid(n / kEPT);
     hipStream_t st = (hipStream_t)stream;
-    switch (w_dt) {
+    switch (w_dt) {   // 16-bit weights only
         case AR_DT_BF16: hipLaunchKernelGGL(k_pack_fp4<AR_DT_BF16>, grid, kTPB, 0, st, Wq, scale, global_scale_dev, n, gs, mode, (uint32_t*)packed, scale_bytes); break;
         case AR_DT_F16: hipLaunchKernelGGL(k_pack_fp4<AR_DT_F16>, grid, kTPB, 0, st, Wq, scale, global_scale_dev, n, gs, mode, (uint32_t*)packed, scale_bytes); break;
         default: return AR_ERR_UNSUPPORTED;
@@ -478,21 +464,14 @@ extern "C" int ar_qdq_fp4_bwd_sgd(const void* dXq, const void* X, float* V, cons
     a.lr_v = lr_v_dev; a.lr_mm = lr_mm_dev; a.snap = snapshot_flag; a.best_V = best_V; a.best_max = best_max;
     a.dV_out = dV_out; a.dmax_out = dmax_out; a.n_groups = n_groups; a.cpg = gs / kEPT; a.mode = mode;
     a.tune_minmax = tune_minmax; a.init_scale = init_scale; a.lo = lo_bound; a.hi = hi_bound;
-    const int grid = fp4_grid((n_groups * a.cpg + AR_FP4_BWD_UNROLL - 1) / AR_FP4_BWD_UNROLL);
+    const int grid = fp4_grid((n_groups * a.cpg + kFp4BwdUnroll - 1) / kFp4BwdUnroll);
     hipStream_t st = (hipStream_t)stream;
-#define AR_BWD(DT)                                                                                                   \
-    do {                                                                                                             \
-        if (mode == 0) AR_LAUNCH_PROF(AR_PROF_FP4_BWD, n_groups, (k_fp4_bwd<DT, AR_FP4_BWD_UNROLL, 0>), grid, kTPB, 0, st, a); \
-        else AR_LAUNCH_PROF(AR_PROF_FP4_BWD, n_groups, (k_fp4_bwd<DT, AR_FP4_BWD_UNROLL, 1>), grid, kTPB, 0, st, a); \
-    } while (0)
-    switch (x_dt) {
-        case AR_DT_BF16: AR_BWD(AR_DT_BF16); break;
-        case AR_DT_F16: AR_BWD(AR_DT_F16); break;
-        case AR_DT_F32: AR_BWD(AR_DT_F32); break;
-        default: return AR_ERR_UNSUPPORTED;
-    }
-#undef AR_BWD
-    return launch_status();
+    const bool known = dispatch_dt(x_dt, [&](auto xt) {
+        constexpr int DT = decltype(xt)::value;
+        if (mode == 0) AR_LAUNCH_PROF(AR_PROF_FP4_BWD, n_groups, (k_fp4_bwd<DT, kFp4BwdUnroll, 0>), grid, kTPB, 0, st, a);
+        else AR_LAUNCH_PROF(AR_PROF_FP4_BWD, n_groups, (k_fp4_bwd<DT, kFp4BwdUnroll, 1>), grid, kTPB, 0, st, a);
+    });
+    return known ? launch_status() : AR_ERR_UNSUPPORTED;
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -615,21 +594,14 @@ extern "C" int ar_fp4_act_bwd(const void* dXq, const void* X, void* dX, const fl
     if (mode == 1 && !global_scale_dev) return AR_ERR_UNSUPPORTED;
     if (n_groups == 0) return AR_OK;
     const int cpg = gs / kEPT;
-    const int grid = fp4_grid((n_groups * cpg + AR_FP4_ABWD_UNROLL - 1) / AR_FP4_ABWD_UNROLL);
+    const int grid = fp4_grid((n_groups * cpg + kFp4ActBwdUnroll - 1) / kFp4ActBwdUnroll);
     hipStream_t st = (hipStream_t)stream;
-#define AR_ABWD(DT)                                                                                                  \
-    do {                                                                                                             \
-        if (mode == 0) hipLaunchKernelGGL((k_fp4_act_bwd<DT, AR_FP4_ABWD_UNROLL, 0>), grid, kTPB, 0, st, dXq, X, dX, global_scale_dev, n_groups); \
-        else hipLaunchKernelGGL((k_fp4_act_bwd<DT, AR_FP4_ABWD_UNROLL, 1>), grid, kTPB, 0, st, dXq, X, dX, global_scale_dev, n_groups); \
-    } while (0)
-    switch (x_dt) {
-        case AR_DT_BF16: AR_ABWD(AR_DT_BF16); break;
-        case AR_DT_F16: AR_ABWD(AR_DT_F16); break;
-        case AR_DT_F32: AR_ABWD(AR_DT_F32); break;
-        default: return AR_ERR_UNSUPPORTED;
-    }
-#undef AR_ABWD
-    return launch_status();
+    const bool known = dispatch_dt(x_dt, [&](auto xt) {
+        constexpr int DT = decltype(xt)::value;
+        if (mode == 0) hipLaunchKernelGGL((k_fp4_act_bwd<DT, kFp4ActBwdUnroll, 0>), grid, kTPB, 0, st, dXq, X, dX, global_scale_dev, n_groups);
+        else hipLaunchKernelGGL((k_fp4_act_bwd<DT, kFp4ActBwdUnroll, 1>), grid, kTPB, 0, st, dXq, X, dX, global_scale_dev, n_groups);
+    });
+    return known ? launch_status() : AR_ERR_UNSUPPORTED;
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -694,11 +666,9 @@ extern "C" int ar_search_fp4_scale(const void* X, const float* absmax, const flo
     const int cpg = gs / kEPT;
     const int grid = fp4_grid(n_groups * cpg);
     hipStream_t st = (hipStream_t)stream;
-    switch (x_dt) {
-        case AR_DT_BF16: hipLaunchKernelGGL(k_search_fp4_scale<AR_DT_BF16>, grid, kTPB, 0, st, X, absmax, qw_row, groups_per_row, global_scale_dev, candidates_dev, n_candidates, best_out, n_groups, cpg, mode); break;
-        case AR_DT_F16: hipLaunchKernelGGL(k_search_fp4_scale<AR_DT_F16>, grid, kTPB, 0, st, X, absmax, qw_row, groups_per_row, global_scale_dev, candidates_dev, n_candidates, best_out, n_groups, cpg, mode); break;
-        case AR_DT_F32: hipLaunchKernelGGL(k_search_fp4_scale<AR_DT_F32>, grid, kTPB, 0, st, X, absmax, qw_row, groups_per_row, global_scale_dev, candidates_dev, n_candidates, best_out, n_groups, cpg, mode); break;
-        default: return AR_ERR_UNSUPPORTED;
-    }
-    return launch_status();
+    const bool known = dispatch_dt(x_dt, [&](auto xt) {
+        hipLaunchKernelGGL(k_search_fp4_scale<decltype(xt)::value>, grid, kTPB, 0, st, X, absmax, qw_row, groups_per_row, global_scale_dev,
+                           candidates_dev, n_candidates, best_out, n_groups, cpg, mode);
+    });
+    return known ? launch_status() : AR_ERR_UNSUPPORTED;
 }

@@ -1,21 +1,22 @@
 // ar_int.hip -- INT (W2/W3/W4/W8, sym + asym) fake-quant kernels for gfx950:
 //   k_group_minmax : per-group min/max (wave shuffle reductions)
-//   k_int_fwd      : K1  fake-quant forward                    8 B/elem + 12 B/group   (HBM bound)
-//   k_int_bwd      : K2(+K3) backward [+ sign-SGD + best-param snapshot + next forward], 12 B/elem + 8 B/group
+//   k_int_fwd*     : K1  fake-quant forward                    8 B/elem + 12 B/group   (HBM bound)
+//   k_int_bwd*     : K2(+K3) backward [+ sign-SGD + best-param snapshot + next forward], 12 B/elem + 8 B/group
 //
-// Two implementations of the hot pair are kept and selectable at build time (AR_INT_FLAT):
-//  * flat (default, faster): every lane issues its 16-byte streaming loads up front, derives its group's (scale, zp)
-//    itself from four broadcast-loaded group parameters, and the gs/8 lanes of a group meet only in the shuffle
-//    butterfly; no LDS, no barrier (k_int_fwd_flat / k_int_bwd_flat).
-//  * LDS-tiled (the first design): the weight is a flat array of groups; a workgroup (256 lanes = 4 waves) owns a
-//    tile of up to 8192 consecutive elements (whole groups).  Per tile:
+// Which kernel a group size takes (cpg = gs / 8 chunks of 16 bytes per group; kTPB * kTiledFwdUnroll = 1024 chunks = 8192 elements):
+//   forward   cpg a power of two <= 64 (lane groups: gs 8 .. 512)   k_int_fwd_flat
+//             any other cpg <= 1024 (gs 24, 40, 1536, 4096, ...)    k_int_fwd          LDS-tiled
+//             cpg > 1024 (per-channel rows of 11008, 28672)         k_int_fwd_generic  one wave per group
+//   backward  lane groups                                           k_int_bwd_flat     (+ sign-SGD, snapshot, next forward)
+//             everything else                                       k_int_bwd_generic  one wave per group, no fused next forward
+//  * flat (the hot pair): every lane issues its 16-byte streaming loads up front, derives its group's (scale, zp) itself from four
+//    broadcast-loaded group parameters, and the gs/8 lanes of a group meet only in the shuffle butterfly; no LDS, no barrier.
+//  * LDS-tiled forward: a workgroup (256 lanes = 4 waves) owns a tile of up to 8192 consecutive elements (whole groups).  Per tile:
 //   (A) up to 256 "group lanes" load the 4 per-group parameters and                      [12 B/group]
-//   (B) every lane issues all of its 16-byte streaming loads (W, V[, dWq]) up front,     [the HBM stream]
+//   (B) every lane issues all of its 16-byte streaming loads (W, V) up front,            [the HBM stream]
 //   (C) the group lanes turn the parameters into (scale, zp) -- fp16 cast, threshold clamp, true IEEE division,
 //       all the data-dependent branching -- and stage them in LDS while the streaming loads are in flight,
 //   (D) one barrier, then every lane consumes its registers against the LDS-staged scales and stores 16 B.
-// The backward additionally reduces 2-4 per-group sums with a DPP/bpermute butterfly over the gs/8 lanes that share
-// a group, hands them to the group lane through LDS, and the group lane applies the sign step to min/max scale.
 // There is no inter-workgroup reuse, so no XCD-aware remap is needed: consecutive tiles simply round-robin over the
 // 8 XCDs and stream straight from HBM.
 #include "ar_common.hpp"
@@ -173,7 +174,6 @@ __device__ __forceinline__ void qdq8_impl(const float (&w)[8], const float (&v)[
 template <int XR>
 __device__ __forceinline__ void qdq8(const float (&w)[8], const float (&v)[8], float s, float zp, float qlo, float qhi,
                                      float (&o)[8]) {
-#if AR_FASTDIV
     bool ok = true;
 #pragma unroll
     for (int k = 0; k < 8; ++k) ok = ok && div_fast_ok(w[k]);
@@ -181,18 +181,12 @@ __device__ __forceinline__ void qdq8(const float (&w)[8], const float (&v)[8], f
         qdq8_impl<XR, true>(w, v, s, 1.0f / s, zp, qlo, qhi, o);
         return;
     }
-#endif
     qdq8_impl<XR, false>(w, v, s, 0.f, zp, qlo, qhi, o);
 }
 
-#ifndef AR_FWD_MINW
-#define AR_FWD_MINW 1
-#endif
-#ifndef AR_BWD_MINW
-#define AR_BWD_MINW 1
-#endif
+constexpr int kTiledFwdMinWaves = 1;   // second argument of the tiled forward's __launch_bounds__
 template <int WDT, int XR, int UNROLL>
-__global__ __launch_bounds__(kTPB, AR_FWD_MINW) void k_int_fwd(const FwdArgs a) {
+__global__ __launch_bounds__(kTPB, kTiledFwdMinWaves) void k_int_fwd(const FwdArgs a) {
     __shared__ float2 sg[2][kTPB];
     const int tid = threadIdx.x;
     const int cpg = a.cpg, shift = a.cpg_shift;
@@ -305,7 +299,6 @@ __device__ __forceinline__ void bwd8_impl(const float (&g)[8], const float (&w)[
 template <int XR>
 __device__ __forceinline__ void bwd8(const float (&g)[8], const float (&w)[8], const float (&v)[8], float s, float zp,
                                      float qlo, float qhi, float (&dy)[8], Sums& acc, bool tree = false) {
-#if AR_FASTDIV
     bool ok = true;
 #pragma unroll
     for (int k = 0; k < 8; ++k) ok = ok && div_fast_ok(w[k]);
@@ -314,7 +307,6 @@ __device__ __forceinline__ void bwd8(const float (&g)[8], const float (&w)[8], c
         else bwd8_impl<XR, true, false>(g, w, v, s, 1.0f / s, zp, qlo, qhi, dy, acc);
         return;
     }
-#endif
     if (tree) bwd8_impl<XR, false, true>(g, w, v, s, 0.f, zp, qlo, qhi, dy, acc);
     else bwd8_impl<XR, false, false>(g, w, v, s, 0.f, zp, qlo, qhi, dy, acc);
 }
@@ -360,135 +352,11 @@ __device__ __forceinline__ void minmax_grads(const IntCfg& cfg, const GroupQ& q,
     }
 }
 
-template <int WDT, int XR, int UNROLL>
-__global__ __launch_bounds__(kTPB, AR_BWD_MINW) void k_int_bwd(const BwdArgs a) {
-    __shared__ float2 sg[kTPB];        // (scale, zp) of the tile's groups
-    __shared__ float4 ssum[kTPB];      // per-group reduced sums, written by the first lane of each lane-group
-    __shared__ float2 sg2[kTPB];       // updated (scale, zp) for the fused next forward
-    const int tid = threadIdx.x;
-    const int cpg = a.cpg, shift = a.cpg_shift;      // cpg is a power of two <= 64 here
-    const int u_eff = cpg < UNROLL ? cpg : UNROLL;
-    const int tile_chunks = kTPB * u_eff;
-    const int tile_groups = tile_chunks >> shift;    // <= kTPB
-    const int64_t total_chunks = a.n_groups << shift;
-    const int64_t n_tiles = (a.n_groups + tile_groups - 1) / tile_groups;
-    const bool sym = a.cfg.sym != 0;
-    const bool do_snap = a.snap != nullptr && *a.snap != 0;
-    const float alpha_v = a.lr_v ? -(*a.lr_v) : 0.f;
-    const float alpha_mm = a.lr_mm ? -(*a.lr_mm) : 0.f;
-
-    for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const int64_t c0 = tile * (int64_t)tile_chunks;
-        const int64_t g = tile * tile_groups + tid;
-        const bool has_g = tid < tile_groups && g < a.n_groups;
-        float wmn = 0.f, wmx = 0.f, ms = 1.f, Ms = 1.f;
-        if (has_g) {
-            wmn = load1<WDT>(a.wmin, g);
-            wmx = load1<WDT>(a.wmax, g);
-            if (a.min_s) ms = a.min_s[g];
-            if (a.max_s) Ms = a.max_s[g];
-        }
-        Raw8<WDT> gr[UNROLL], wr[UNROLL];
-        F8 vr[UNROLL];
-        bool ok[UNROLL];
-#pragma unroll
-        for (int u = 0; u < UNROLL; ++u) {
-            const int64_t c = c0 + u * kTPB + tid;
-            ok[u] = (u < u_eff) && (c < total_chunks);
-            if (ok[u]) {
-                gr[u] = load8_raw<WDT>(a.dWq, c * kEPT);
-                wr[u] = load8_raw<WDT>(a.W, c * kEPT);
-                if (a.V) vr[u] = load8_f32(a.V, c * kEPT);
-            }
-        }
-        GroupQ q;
-        if (has_g) {
-            group_scale(a.cfg, wmn, wmx, ms, Ms, q);
-            sg[tid] = make_float2(q.s, sym ? 0.f : q.zp);
-        }
-        __syncthreads();
-
-        float vnew[UNROLL][8];
-#pragma unroll
-        for (int u = 0; u < UNROLL; ++u) {
-            // every lane of a lane-group must take part in the butterfly, so no early `continue` here
-            const int gl = (u * kTPB + tid) >> shift;
-            const float2 sz = sg[gl < tile_groups ? gl : 0];
-            float gg[8], w[8], v[8], dy[8];
-            Sums acc = {0.f, 0.f, 0.f, 0.f};
-            if (ok[u]) {
-                unpack8<WDT>(gr[u], gg);
-                unpack8<WDT>(wr[u], w);
-                if (a.V) unpack_f8(vr[u], v);
-                else {
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) v[k] = 0.f;
-                }
-                bwd8<XR>(gg, w, v, sz.x, sz.y, a.qlo, a.qhi, dy, acc, a.cpg <= 8);
-                const int64_t e0 = (c0 + u * kTPB + tid) * kEPT;
-                if (a.dV) store8_f32(a.dV, e0, dy);
-                if (a.lr_v) {
-                    if (do_snap && a.best_V) store8_f32(a.best_V, e0, v);   // pre-update V == the best iterate
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) vnew[u][k] = v[k] + alpha_v * sgnf(dy[k]);
-                    store8_f32(a.V, e0, vnew[u]);
-                } else {
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) vnew[u][k] = v[k];
-                }
-            }
-            if (u < u_eff) {   // wave-uniform
-                acc.c1 = lanes_sum_torch(acc.c1, cpg);
-                acc.c2 = lanes_sum_torch(acc.c2, cpg);
-                if (!sym) { acc.e = lanes_sum_torch(acc.e, cpg); acc.dy = lanes_sum_torch(acc.dy, cpg); }
-                if ((tid & (cpg - 1)) == 0 && gl < tile_groups) ssum[gl] = make_float4(acc.c1, acc.c2, acc.e, acc.dy);
-            }
-        }
-        __syncthreads();
-
-        if (has_g) {
-            float gmin, gmax;
-            minmax_grads<XR>(a.cfg, q, ssum[tid], gmin, gmax);
-            if (a.dmin) a.dmin[g] = gmin;
-            if (a.dmax) a.dmax[g] = gmax;
-            float ms_new = ms, Ms_new = Ms;
-            if (a.lr_mm && a.tune_minmax) {
-                if (do_snap) {
-                    if (a.best_min) a.best_min[g] = q.ms;
-                    if (a.best_max) a.best_max[g] = q.Ms;
-                }
-                ms_new = q.ms + alpha_mm * sgnf(gmin);   // the clamp happened "in place" at the forward
-                Ms_new = q.Ms + alpha_mm * sgnf(gmax);
-                a.min_s[g] = ms_new;
-                a.max_s[g] = Ms_new;
-            }
-            if (a.Wq_next) {
-                GroupQ q2;
-                group_scale(a.cfg, wmn, wmx, ms_new, Ms_new, q2);
-                sg2[tid] = make_float2(q2.s, sym ? 0.f : q2.zp);
-            }
-        }
-        if (a.Wq_next) {   // kernel-uniform
-            __syncthreads();
-#pragma unroll
-            for (int u = 0; u < UNROLL; ++u) {
-                if (!ok[u]) continue;
-                const float2 sz = sg2[(u * kTPB + tid) >> shift];
-                float w[8], o[8];
-                unpack8<WDT>(wr[u], w);
-                qdq8<XR>(w, vnew[u], sz.x, sz.y, a.qlo, a.qhi, o);
-                store8<WDT>(a.Wq_next, (c0 + u * kTPB + tid) * kEPT, o);
-            }
-        }
-        __syncthreads();   // sg / ssum / sg2 are reused by the next tile
-    }
-}
-
-
 // ------------------------------------------------------------------------------------------------------------------
-// generic group sizes (any multiple of 8: per-channel rows of 11008 / 28672, non power-of-two groups, gs > 512):
-// one wave owns one group and strides over its chunks; same arithmetic, same LDS-free wave reductions.  Slower per
-// byte than the tiled kernels (one group's parameters per wave), used only where those do not apply.
+// one wave per group (any multiple of 8): one wave owns one group and strides over its chunks; same arithmetic, LDS-free wave
+// reductions.  Slower per byte than the flat and tiled kernels (one group's parameters per wave), used only where those do not apply:
+//   forward   groups longer than kTPB * kTiledFwdUnroll chunks (per-channel rows of 11008 / 28672)
+//   backward  every group that is not a lane group (non power-of-two chunks, gs > 512); it has no fused next forward
 // ------------------------------------------------------------------------------------------------------------------
 template <int WDT, int XR>
 __global__ __launch_bounds__(kTPB) void k_int_fwd_generic(const FwdArgs a) {
@@ -577,10 +445,11 @@ __global__ __launch_bounds__(kTPB) void k_int_bwd_generic(const BwdArgs a) {
 
 
 // ------------------------------------------------------------------------------------------------------------------
-// "flat" variants of the two hot kernels (AR_INT_FLAT=1): no LDS tile, no barrier.  Every lane derives the (scale, zp)
+// flat kernels, the hot pair (lane groups): no LDS tile, no barrier.  Every lane derives the (scale, zp)
 // of its chunk's group itself from the four group parameters (broadcast loads; gs/8 lanes repeat the same ~40 VALU
 // operations), the gs/8 lanes of a group meet only in the shuffle butterfly, and the first lane of the group applies
-// the min/max step.  A/B against the LDS-staged kernels is recorded in DESIGN.md section 3.
+// the min/max step.  A/B against LDS-staged kernels (MI355X, Llama-3-8B block, same session):
+//   forward 5.82 vs 5.44 TB/s, fused backward+sign-SGD 5.02 vs 4.70 TB/s, backward+next-forward 5.12 vs 4.83 TB/s.
 // ------------------------------------------------------------------------------------------------------------------
 // SPEC != 0: instantiation for the configurations the BASELINE runs use -- symmetric, fp16 scales, SPEC lanes per group
 // (16 = group 128, 4 = group 32): the scheme branches, the runtime scale-dtype rounding and the butterfly width fold at
@@ -758,13 +627,12 @@ static inline int ilog2_exact(int v) {
     return s;
 }
 static inline int promote_dt(int a, int b) { return a == b ? a : AR_DT_F32; }
-static inline int grid_for_tiles(int64_t n_tiles) {
-#ifndef AR_GRID_CAP
-#define AR_GRID_CAP (1 << 24)      // effectively one tile per workgroup (measured: >= the capped grid-stride form)
-#endif
-    const int64_t cap = AR_GRID_CAP;
-    return (int)(n_tiles < cap ? (n_tiles > 0 ? n_tiles : 1) : cap);
-}
+constexpr int64_t kGridCap = 1 << 24;   // effectively one tile per workgroup (measured: >= the capped grid-stride form)
+static inline int grid_for_tiles(int64_t n_tiles) { return (int)(n_tiles < kGridCap ? (n_tiles > 0 ? n_tiles : 1) : kGridCap); }
+// chunks per lane in flight
+constexpr int kFlatFwdUnroll = 1;
+constexpr int kFlatBwdUnroll = 2;
+constexpr int kTiledFwdUnroll = 4;
 static inline bool fill_cfg(IntCfg& c, float& qlo, float& qhi, int bits, int sym, int w_dt, int s_dt, float th, float lo,
                             float hi) {
     if (bits < 2 || bits > 8) return false;
@@ -779,100 +647,53 @@ static inline bool fill_cfg(IntCfg& c, float& qlo, float& qhi, int bits, int sym
 
 using namespace ar;
 
-// lane groups (power-of-two chunks per group up to a wave): the templated kernel, four loads per lane in flight
-template <int WDT>
-static bool launch_minmax_lg(const void* W, void* wmin, void* wmax, float* absmax, float* tensor_absmax, int64_t n_groups, int cpg,
-                             hipStream_t st) {
-    constexpr int U = 4;
-    const int64_t chunks = n_groups * cpg;
-    int64_t blocks = (chunks + (int64_t)kTPB * U - 1) / ((int64_t)kTPB * U);
-    if (blocks < 1) blocks = 1;
-    if (tensor_absmax && blocks > 256 * 8) blocks = 256 * 8;    // grid-stride: at most 2048 atomics on the global max
-    if (blocks > (1 << 22)) blocks = 1 << 22;
-    const int grid = (int)blocks;
-#define AR_MM(C) hipLaunchKernelGGL((k_group_minmax_lg<WDT, C, U>), grid, kTPB, 0, st, W, wmin, wmax, absmax, tensor_absmax, n_groups)
-    switch (cpg) {
-        case 1: AR_MM(1); break;
-        case 2: AR_MM(2); break;
-        case 4: AR_MM(4); break;
-        case 8: AR_MM(8); break;
-        case 16: AR_MM(16); break;
-        case 32: AR_MM(32); break;
-        case 64: AR_MM(64); break;
-        default: return false;
-    }
+// group min/max and abs-max.  Lane groups (power-of-two chunks per group up to a wave): the templated kernel, four loads per lane in
+// flight; every other group size: one wave per group (k_group_minmax, told so by a negative cpg).
+static int launch_minmax(const void* W, void* wmin, void* wmax, float* absmax, float* tensor_absmax, int64_t n_groups, int gs, int w_dt,
+                         ar_stream_t stream) {
+    if (gs <= 0 || gs % kEPT || n_groups < 0) return AR_ERR_UNSUPPORTED;
+    if (n_groups == 0) return AR_OK;
+    const int cpg = gs / kEPT;
+    hipStream_t st = (hipStream_t)stream;
+    constexpr int kMaxAtomicBlocks = 256 * 8;    // grid-stride: at most 2048 atomics on the global max
+    bool known;
+    if (cpg <= kWave && ilog2_exact(cpg) >= 0) {
+        constexpr int U = 4;
+        int64_t blocks = (n_groups * cpg + (int64_t)kTPB * U - 1) / ((int64_t)kTPB * U);
+        if (blocks < 1) blocks = 1;
+        if (tensor_absmax && blocks > kMaxAtomicBlocks) blocks = kMaxAtomicBlocks;
+        if (blocks > (1 << 22)) blocks = 1 << 22;
+        const int grid = (int)blocks;
+        known = dispatch_dt(w_dt, [&](auto wt) {
+            constexpr int WDT = decltype(wt)::value;
+#define AR_MM(C) case C: hipLaunchKernelGGL((k_group_minmax_lg<WDT, C, U>), grid, kTPB, 0, st, W, wmin, wmax, absmax, tensor_absmax, n_groups); break
+            switch (cpg) { AR_MM(1); AR_MM(2); AR_MM(4); AR_MM(8); AR_MM(16); AR_MM(32); AR_MM(64); }
 #undef AR_MM
-    return true;
-}
-static bool launch_minmax_lg(const void* W, void* wmin, void* wmax, float* absmax, float* tensor_absmax, int64_t n_groups, int cpg,
-                             int w_dt, hipStream_t st) {
-    switch (w_dt) {
-        case AR_DT_BF16: return launch_minmax_lg<AR_DT_BF16>(W, wmin, wmax, absmax, tensor_absmax, n_groups, cpg, st);
-        case AR_DT_F16: return launch_minmax_lg<AR_DT_F16>(W, wmin, wmax, absmax, tensor_absmax, n_groups, cpg, st);
-        case AR_DT_F32: return launch_minmax_lg<AR_DT_F32>(W, wmin, wmax, absmax, tensor_absmax, n_groups, cpg, st);
-        default: return false;
+        });
+    } else {
+        int grid = grid_for_tiles((n_groups + 3) / 4);
+        if (tensor_absmax && grid > kMaxAtomicBlocks) grid = kMaxAtomicBlocks;
+        known = dispatch_dt(w_dt, [&](auto wt) {
+            hipLaunchKernelGGL(k_group_minmax<decltype(wt)::value>, grid, kTPB, 0, st, W, wmin, wmax, absmax, tensor_absmax, n_groups, -cpg);
+        });
     }
+    return known ? launch_status() : AR_ERR_UNSUPPORTED;
 }
 
 extern "C" int ar_group_minmax(const void* W, void* wmin, void* wmax, int64_t n_groups, int gs, int w_dt,
                                ar_stream_t stream) {
-    if (gs <= 0 || gs % kEPT || n_groups < 0) return AR_ERR_UNSUPPORTED;
-    if (n_groups == 0) return AR_OK;
-    const int cpg = gs / kEPT;
-    const bool lane_groups = cpg <= kWave && ilog2_exact(cpg) >= 0;
-    if (lane_groups && launch_minmax_lg(W, wmin, wmax, nullptr, nullptr, n_groups, cpg, w_dt, (hipStream_t)stream)) return launch_status();
-    const int64_t waves = lane_groups ? (n_groups + (kWave / cpg) - 1) / (kWave / cpg) : n_groups;
-    const int grid = grid_for_tiles((waves + 3) / 4);
-    hipStream_t st = (hipStream_t)stream;
-    switch (w_dt) {
-        case AR_DT_BF16: hipLaunchKernelGGL(k_group_minmax<AR_DT_BF16>, grid, kTPB, 0, st, W, wmin, wmax, nullptr, nullptr, n_groups, lane_groups ? cpg : -cpg); break;
-        case AR_DT_F16: hipLaunchKernelGGL(k_group_minmax<AR_DT_F16>, grid, kTPB, 0, st, W, wmin, wmax, nullptr, nullptr, n_groups, lane_groups ? cpg : -cpg); break;
-        case AR_DT_F32: hipLaunchKernelGGL(k_group_minmax<AR_DT_F32>, grid, kTPB, 0, st, W, wmin, wmax, nullptr, nullptr, n_groups, lane_groups ? cpg : -cpg); break;
-        default: return AR_ERR_UNSUPPORTED;
-    }
-    return launch_status();
+    return launch_minmax(W, wmin, wmax, nullptr, nullptr, n_groups, gs, w_dt, stream);
 }
 
 extern "C" int ar_group_absmax(const void* W, float* absmax, float* tensor_absmax, int64_t n_groups, int gs, int w_dt,
                                ar_stream_t stream) {
-    if (gs <= 0 || gs % kEPT || n_groups < 0) return AR_ERR_UNSUPPORTED;
-    if (n_groups == 0) return AR_OK;
-    const int cpg = gs / kEPT;
-    const bool lane_groups = cpg <= kWave && ilog2_exact(cpg) >= 0;
-    if (lane_groups && launch_minmax_lg(W, nullptr, nullptr, absmax, tensor_absmax, n_groups, cpg, w_dt, (hipStream_t)stream)) return launch_status();
-    const int64_t waves = lane_groups ? (n_groups + (kWave / cpg) - 1) / (kWave / cpg) : n_groups;
-    int grid = grid_for_tiles((waves + 3) / 4);
-    if (tensor_absmax && grid > 256 * 8) grid = 256 * 8;   // grid-stride: at most 2048 atomics on the global max
-    hipStream_t st = (hipStream_t)stream;
-    switch (w_dt) {
-        case AR_DT_BF16: hipLaunchKernelGGL(k_group_minmax<AR_DT_BF16>, grid, kTPB, 0, st, W, nullptr, nullptr, absmax, tensor_absmax, n_groups, lane_groups ? cpg : -cpg); break;
-        case AR_DT_F16: hipLaunchKernelGGL(k_group_minmax<AR_DT_F16>, grid, kTPB, 0, st, W, nullptr, nullptr, absmax, tensor_absmax, n_groups, lane_groups ? cpg : -cpg); break;
-        case AR_DT_F32: hipLaunchKernelGGL(k_group_minmax<AR_DT_F32>, grid, kTPB, 0, st, W, nullptr, nullptr, absmax, tensor_absmax, n_groups, lane_groups ? cpg : -cpg); break;
-        default: return AR_ERR_UNSUPPORTED;
-    }
-    return launch_status();
+    return launch_minmax(W, nullptr, nullptr, absmax, tensor_absmax, n_groups, gs, w_dt, stream);
 }
 
-// AR_INT_FLAT=1 (default): the flat kernels; 0: the LDS-tiled ones.  A/B on MI355X, Llama-3-8B block, same session:
-//   forward 5.82 vs 5.44 TB/s, fused backward+sign-SGD 5.02 vs 4.70 TB/s, backward+next-forward 5.12 vs 4.83 TB/s.
-#ifndef AR_INT_FLAT
-#define AR_INT_FLAT 1
-#endif
-#ifndef AR_FLAT_FWD_UNROLL
-#define AR_FLAT_FWD_UNROLL 1
-#endif
-#ifndef AR_FLAT_BWD_UNROLL
-#define AR_FLAT_BWD_UNROLL 2
-#endif
-#ifndef AR_INT_SPEC
-#define AR_INT_SPEC 1
-#endif
-#ifndef AR_FWD_UNROLL
-#define AR_FWD_UNROLL 4
-#endif
-#ifndef AR_BWD_UNROLL
-#define AR_BWD_UNROLL 2
-#endif
+// W/scale is evaluated in torch's promoted dtype: the 16-bit type when weight and scale share it, else fp32
+static inline bool same16_of(int w_dt, int s_dt) { return w_dt == s_dt && w_dt != AR_DT_F32; }
+// the configuration the BASELINE runs use, for which the flat kernels have SPEC instantiations (SPEC = lanes per group)
+static inline bool is_spec_cfg(const IntCfg& c) { return c.w_dt == AR_DT_BF16 && c.s_dt == AR_DT_F16 && c.sym == 1; }
 
 extern "C" int ar_qdq_int_fwd(const void* W, const float* V, const void* wmin, const void* wmax, const float* min_s,
                               const float* max_s, void* Wq, void* scale_out, float* zp_out, int64_t n_groups, int gs,
@@ -885,65 +706,38 @@ extern "C" int ar_qdq_int_fwd(const void* W, const float* V, const void* wmin, c
     a.W = W; a.V = V; a.wmin = wmin; a.wmax = wmax; a.min_s = min_s; a.max_s = max_s; a.Wq = Wq;
     a.scale_out = scale_out; a.zp_out = zp_out; a.n_groups = n_groups;
     a.cpg = gs / kEPT; a.cpg_shift = ilog2_exact(a.cpg); a.x_dt = promote_dt(w_dt, s_dt);
-    const int u_eff = a.cpg < AR_FWD_UNROLL ? a.cpg : AR_FWD_UNROLL;
-    int tile_groups = kTPB * u_eff / a.cpg;
-    if (tile_groups < 1) tile_groups = 1;
-    const int grid = grid_for_tiles((n_groups + tile_groups - 1) / tile_groups);
     hipStream_t st = (hipStream_t)stream;
-    // W/scale is evaluated in torch's promoted dtype: the 16-bit type when weight and scale share it, else fp32
-    const bool same16 = (a.x_dt == w_dt) && (w_dt != AR_DT_F32);
-    if (a.cpg > kTPB * AR_FWD_UNROLL) {   // very long groups (per-channel rows): one wave per group
-        const int ggrid = grid_for_tiles((n_groups + 3) / 4);
-        switch (w_dt) {
-            case AR_DT_BF16:
-                if (same16) hipLaunchKernelGGL((k_int_fwd_generic<AR_DT_BF16, AR_DT_BF16>), ggrid, kTPB, 0, st, a);
-                else hipLaunchKernelGGL((k_int_fwd_generic<AR_DT_BF16, AR_DT_F32>), ggrid, kTPB, 0, st, a);
-                break;
-            case AR_DT_F16:
-                if (same16) hipLaunchKernelGGL((k_int_fwd_generic<AR_DT_F16, AR_DT_F16>), ggrid, kTPB, 0, st, a);
-                else hipLaunchKernelGGL((k_int_fwd_generic<AR_DT_F16, AR_DT_F32>), ggrid, kTPB, 0, st, a);
-                break;
-            default: hipLaunchKernelGGL((k_int_fwd_generic<AR_DT_F32, AR_DT_F32>), ggrid, kTPB, 0, st, a); break;
-        }
-        return launch_status();
-    }
-#if AR_INT_FLAT
-    if (a.cpg_shift >= 0 && a.cpg <= kWave) {
-        const int fgrid = grid_for_tiles((n_groups * a.cpg + kTPB * AR_FLAT_FWD_UNROLL - 1) / (kTPB * AR_FLAT_FWD_UNROLL));
-#if AR_INT_SPEC
+    const bool same16 = same16_of(w_dt, s_dt);
+    bool known;
+    if (a.cpg_shift >= 0 && a.cpg <= kWave) {             // lane groups: flat
+        const int grid = grid_for_tiles((n_groups * a.cpg + kTPB * kFlatFwdUnroll - 1) / (kTPB * kFlatFwdUnroll));
         // measured (tools/kbench.py): the forward is HBM-bound either way (group 128: equal, group 32: the generic one is
         // 1.7 % faster), the fused backward gains 4-9 % -- so only group 128 takes the specialised forward
-        if (w_dt == AR_DT_BF16 && !same16 && a.cfg.sym == 1 && s_dt == AR_DT_F16 && a.cpg == 16) {
-            AR_LAUNCH_PROF(AR_PROF_INT_FWD, a.n_groups, (k_int_fwd_flat<AR_DT_BF16, AR_DT_F32, AR_FLAT_FWD_UNROLL, 16>), fgrid, kTPB, 0, st, a);
+        if (is_spec_cfg(a.cfg) && a.cpg == 16) {
+            AR_LAUNCH_PROF(AR_PROF_INT_FWD, a.n_groups, (k_int_fwd_flat<AR_DT_BF16, AR_DT_F32, kFlatFwdUnroll, 16>), grid, kTPB, 0, st, a);
             return launch_status();
         }
-#endif
-        switch (w_dt) {
-            case AR_DT_BF16:
-                if (same16) AR_LAUNCH_PROF(AR_PROF_INT_FWD, a.n_groups, (k_int_fwd_flat<AR_DT_BF16, AR_DT_BF16, AR_FLAT_FWD_UNROLL>), fgrid, kTPB, 0, st, a);
-                else AR_LAUNCH_PROF(AR_PROF_INT_FWD, a.n_groups, (k_int_fwd_flat<AR_DT_BF16, AR_DT_F32, AR_FLAT_FWD_UNROLL>), fgrid, kTPB, 0, st, a);
-                break;
-            case AR_DT_F16:
-                if (same16) AR_LAUNCH_PROF(AR_PROF_INT_FWD, a.n_groups, (k_int_fwd_flat<AR_DT_F16, AR_DT_F16, AR_FLAT_FWD_UNROLL>), fgrid, kTPB, 0, st, a);
-                else AR_LAUNCH_PROF(AR_PROF_INT_FWD, a.n_groups, (k_int_fwd_flat<AR_DT_F16, AR_DT_F32, AR_FLAT_FWD_UNROLL>), fgrid, kTPB, 0, st, a);
-                break;
-            default: AR_LAUNCH_PROF(AR_PROF_INT_FWD, a.n_groups, (k_int_fwd_flat<AR_DT_F32, AR_DT_F32, AR_FLAT_FWD_UNROLL>), fgrid, kTPB, 0, st, a); break;
-        }
-        return launch_status();
+        known = dispatch_dt_pair(w_dt, same16, [&](auto wt, auto xt) {
+            constexpr int WDT = decltype(wt)::value, XR = decltype(xt)::value;
+            AR_LAUNCH_PROF(AR_PROF_INT_FWD, a.n_groups, (k_int_fwd_flat<WDT, XR, kFlatFwdUnroll>), grid, kTPB, 0, st, a);
+        });
+    } else if (a.cpg <= kTPB * kTiledFwdUnroll) {         // other groups that fit a workgroup's tile: LDS-tiled
+        const int u_eff = a.cpg < kTiledFwdUnroll ? a.cpg : kTiledFwdUnroll;
+        int tile_groups = kTPB * u_eff / a.cpg;
+        if (tile_groups < 1) tile_groups = 1;
+        const int grid = grid_for_tiles((n_groups + tile_groups - 1) / tile_groups);
+        known = dispatch_dt_pair(w_dt, same16, [&](auto wt, auto xt) {
+            constexpr int WDT = decltype(wt)::value, XR = decltype(xt)::value;
+            hipLaunchKernelGGL((k_int_fwd<WDT, XR, kTiledFwdUnroll>), grid, kTPB, 0, st, a);
+        });
+    } else {                                              // very long groups (per-channel rows): one wave per group
+        const int grid = grid_for_tiles((n_groups + 3) / 4);
+        known = dispatch_dt_pair(w_dt, same16, [&](auto wt, auto xt) {
+            constexpr int WDT = decltype(wt)::value, XR = decltype(xt)::value;
+            hipLaunchKernelGGL((k_int_fwd_generic<WDT, XR>), grid, kTPB, 0, st, a);
+        });
     }
-#endif
-    switch (w_dt) {
-        case AR_DT_BF16:
-            if (same16) hipLaunchKernelGGL((k_int_fwd<AR_DT_BF16, AR_DT_BF16, AR_FWD_UNROLL>), grid, kTPB, 0, st, a);
-            else hipLaunchKernelGGL((k_int_fwd<AR_DT_BF16, AR_DT_F32, AR_FWD_UNROLL>), grid, kTPB, 0, st, a);
-            break;
-        case AR_DT_F16:
-            if (same16) hipLaunchKernelGGL((k_int_fwd<AR_DT_F16, AR_DT_F16, AR_FWD_UNROLL>), grid, kTPB, 0, st, a);
-            else hipLaunchKernelGGL((k_int_fwd<AR_DT_F16, AR_DT_F32, AR_FWD_UNROLL>), grid, kTPB, 0, st, a);
-            break;
-        default: hipLaunchKernelGGL((k_int_fwd<AR_DT_F32, AR_DT_F32, AR_FWD_UNROLL>), grid, kTPB, 0, st, a); break;
-    }
-    return launch_status();
+    return known ? launch_status() : AR_ERR_UNSUPPORTED;
 }
 
 static int launch_int_bwd(BwdArgs& a, int gs, int bits, int sym, int w_dt, int s_dt, float q_thresh, float lo, float hi,
@@ -952,66 +746,30 @@ static int launch_int_bwd(BwdArgs& a, int gs, int bits, int sym, int w_dt, int s
     if (gs <= 0 || gs % kEPT || a.n_groups < 0) return AR_ERR_UNSUPPORTED;
     a.cpg = gs / kEPT; a.cpg_shift = ilog2_exact(a.cpg); a.x_dt = promote_dt(w_dt, s_dt);
     if (a.n_groups == 0) return AR_OK;
-    if (a.cpg_shift < 0 || a.cpg > kWave) {   // lane-group butterfly needs gs in {8,16,...,512}: otherwise one wave per group
-        if (a.Wq_next) return AR_ERR_UNSUPPORTED;      // the fused next forward exists in the tiled kernel only
-        const bool same16g = (a.x_dt == w_dt) && (w_dt != AR_DT_F32);
-        const int ggrid = grid_for_tiles((a.n_groups + 3) / 4);
-        hipStream_t gst = (hipStream_t)stream;
-        switch (w_dt) {
-            case AR_DT_BF16:
-                if (same16g) hipLaunchKernelGGL((k_int_bwd_generic<AR_DT_BF16, AR_DT_BF16>), ggrid, kTPB, 0, gst, a);
-                else hipLaunchKernelGGL((k_int_bwd_generic<AR_DT_BF16, AR_DT_F32>), ggrid, kTPB, 0, gst, a);
-                break;
-            case AR_DT_F16:
-                if (same16g) hipLaunchKernelGGL((k_int_bwd_generic<AR_DT_F16, AR_DT_F16>), ggrid, kTPB, 0, gst, a);
-                else hipLaunchKernelGGL((k_int_bwd_generic<AR_DT_F16, AR_DT_F32>), ggrid, kTPB, 0, gst, a);
-                break;
-            default: hipLaunchKernelGGL((k_int_bwd_generic<AR_DT_F32, AR_DT_F32>), ggrid, kTPB, 0, gst, a); break;
-        }
-        return launch_status();
-    }
-    const int u_eff = a.cpg < AR_BWD_UNROLL ? a.cpg : AR_BWD_UNROLL;
-    const int tile_groups = kTPB * u_eff / a.cpg;
-    const int grid = grid_for_tiles((a.n_groups + tile_groups - 1) / tile_groups);
     hipStream_t st = (hipStream_t)stream;
-    const bool same16 = (a.x_dt == w_dt) && (w_dt != AR_DT_F32);
-#if AR_INT_FLAT
-    {
-        const int fgrid = grid_for_tiles((a.n_groups * a.cpg + kTPB * AR_FLAT_BWD_UNROLL - 1) / (kTPB * AR_FLAT_BWD_UNROLL));
-#if AR_INT_SPEC
-        if (w_dt == AR_DT_BF16 && !same16 && a.cfg.sym == 1 && s_dt == AR_DT_F16 && (a.cpg == 16 || a.cpg == 4)) {
+    const bool same16 = same16_of(w_dt, s_dt);
+    bool known;
+    if (a.cpg_shift >= 0 && a.cpg <= kWave) {             // lane groups (gs in {8, 16, ..., 512}): flat
+        const int grid = grid_for_tiles((a.n_groups * a.cpg + kTPB * kFlatBwdUnroll - 1) / (kTPB * kFlatBwdUnroll));
+        if (is_spec_cfg(a.cfg) && (a.cpg == 16 || a.cpg == 4)) {
             // (one chunk per lane for small blocks -- OPT-125M's 85 MB stream -- was measured in round 3: 22 vs 21 us, no gain)
-            if (a.cpg == 16) AR_LAUNCH_PROF(AR_PROF_INT_BWD, a.n_groups, (k_int_bwd_flat<AR_DT_BF16, AR_DT_F32, AR_FLAT_BWD_UNROLL, 16>), fgrid, kTPB, 0, st, a);
-            else AR_LAUNCH_PROF(AR_PROF_INT_BWD, a.n_groups, (k_int_bwd_flat<AR_DT_BF16, AR_DT_F32, AR_FLAT_BWD_UNROLL, 4>), fgrid, kTPB, 0, st, a);
+            if (a.cpg == 16) AR_LAUNCH_PROF(AR_PROF_INT_BWD, a.n_groups, (k_int_bwd_flat<AR_DT_BF16, AR_DT_F32, kFlatBwdUnroll, 16>), grid, kTPB, 0, st, a);
+            else AR_LAUNCH_PROF(AR_PROF_INT_BWD, a.n_groups, (k_int_bwd_flat<AR_DT_BF16, AR_DT_F32, kFlatBwdUnroll, 4>), grid, kTPB, 0, st, a);
             return launch_status();
         }
-#endif
-        switch (w_dt) {
-            case AR_DT_BF16:
-                if (same16) AR_LAUNCH_PROF(AR_PROF_INT_BWD, a.n_groups, (k_int_bwd_flat<AR_DT_BF16, AR_DT_BF16, AR_FLAT_BWD_UNROLL>), fgrid, kTPB, 0, st, a);
-                else AR_LAUNCH_PROF(AR_PROF_INT_BWD, a.n_groups, (k_int_bwd_flat<AR_DT_BF16, AR_DT_F32, AR_FLAT_BWD_UNROLL>), fgrid, kTPB, 0, st, a);
-                break;
-            case AR_DT_F16:
-                if (same16) AR_LAUNCH_PROF(AR_PROF_INT_BWD, a.n_groups, (k_int_bwd_flat<AR_DT_F16, AR_DT_F16, AR_FLAT_BWD_UNROLL>), fgrid, kTPB, 0, st, a);
-                else AR_LAUNCH_PROF(AR_PROF_INT_BWD, a.n_groups, (k_int_bwd_flat<AR_DT_F16, AR_DT_F32, AR_FLAT_BWD_UNROLL>), fgrid, kTPB, 0, st, a);
-                break;
-            default: AR_LAUNCH_PROF(AR_PROF_INT_BWD, a.n_groups, (k_int_bwd_flat<AR_DT_F32, AR_DT_F32, AR_FLAT_BWD_UNROLL>), fgrid, kTPB, 0, st, a); break;
-        }
-        return launch_status();
+        known = dispatch_dt_pair(w_dt, same16, [&](auto wt, auto xt) {
+            constexpr int WDT = decltype(wt)::value, XR = decltype(xt)::value;
+            AR_LAUNCH_PROF(AR_PROF_INT_BWD, a.n_groups, (k_int_bwd_flat<WDT, XR, kFlatBwdUnroll>), grid, kTPB, 0, st, a);
+        });
+    } else {                                              // every other group size: one wave per group
+        if (a.Wq_next) return AR_ERR_UNSUPPORTED;         // the fused next forward exists in the flat kernel only
+        const int grid = grid_for_tiles((a.n_groups + 3) / 4);
+        known = dispatch_dt_pair(w_dt, same16, [&](auto wt, auto xt) {
+            constexpr int WDT = decltype(wt)::value, XR = decltype(xt)::value;
+            hipLaunchKernelGGL((k_int_bwd_generic<WDT, XR>), grid, kTPB, 0, st, a);
+        });
     }
-#endif
-    switch (w_dt) {
-        case AR_DT_BF16:
-            if (same16) hipLaunchKernelGGL((k_int_bwd<AR_DT_BF16, AR_DT_BF16, AR_BWD_UNROLL>), grid, kTPB, 0, st, a);
-            else hipLaunchKernelGGL((k_int_bwd<AR_DT_BF16, AR_DT_F32, AR_BWD_UNROLL>), grid, kTPB, 0, st, a);
-            break;
-        case AR_DT_F16:
-            if (same16) hipLaunchKernelGGL((k_int_bwd<AR_DT_F16, AR_DT_F16, AR_BWD_UNROLL>), grid, kTPB, 0, st, a);
-            else hipLaunchKernelGGL((k_int_bwd<AR_DT_F16, AR_DT_F32, AR_BWD_UNROLL>), grid, kTPB, 0, st, a);
-            break;
-        default: hipLaunchKernelGGL((k_int_bwd<AR_DT_F32, AR_DT_F32, AR_BWD_UNROLL>), grid, kTPB, 0, st, a); break;
-    }
-    return launch_status();
+    return known ? launch_status() : AR_ERR_UNSUPPORTED;
 }
 
 extern "C" int ar_qdq_int_bwd(const void* dWq, const void* W, const float* V, const void* wmin, const void* wmax,
@@ -1189,17 +947,12 @@ extern "C" int ar_search_int_scale(const void* X, const float* qw_row, int64_t g
     hipStream_t st = (hipStream_t)stream;
     const int64_t want = lane_groups ? (n_groups * cpg + kTPB - 1) / kTPB : (n_groups + kTPB / kWave - 1) / (kTPB / kWave);
     const int grid = (int)(want < 1 ? 1 : (want > (1 << 20) ? (1 << 20) : want));
-#define AR_LAUNCH_SEARCH(DT)                                                                                              \
-    if (lane_groups) hipLaunchKernelGGL(k_search_int_scale<DT>, grid, kTPB, 0, st, X, qw_row, groups_per_row, candidates_dev, \
-                                        n_candidates, out_raw, out_init, n_groups, cpg, nmax, q_thresh);                  \
-    else hipLaunchKernelGGL(k_search_int_scale_wave<DT>, grid, kTPB, 0, st, X, qw_row, groups_per_row, candidates_dev,    \
-                            n_candidates, out_raw, out_init, n_groups, cpg, nmax, q_thresh)
-    switch (x_dt) {
-        case AR_DT_BF16: AR_LAUNCH_SEARCH(AR_DT_BF16); break;
-        case AR_DT_F16: AR_LAUNCH_SEARCH(AR_DT_F16); break;
-        case AR_DT_F32: AR_LAUNCH_SEARCH(AR_DT_F32); break;
-        default: return AR_ERR_UNSUPPORTED;
-    }
-#undef AR_LAUNCH_SEARCH
-    return launch_status();
+    const bool known = dispatch_dt(x_dt, [&](auto xt) {
+        constexpr int XDT = decltype(xt)::value;
+        if (lane_groups) hipLaunchKernelGGL(k_search_int_scale<XDT>, grid, kTPB, 0, st, X, qw_row, groups_per_row, candidates_dev,
+                                            n_candidates, out_raw, out_init, n_groups, cpg, nmax, q_thresh);
+        else hipLaunchKernelGGL(k_search_int_scale_wave<XDT>, grid, kTPB, 0, st, X, qw_row, groups_per_row, candidates_dev,
+                                n_candidates, out_raw, out_init, n_groups, cpg, nmax, q_thresh);
+    });
+    return known ? launch_status() : AR_ERR_UNSUPPORTED;
 }

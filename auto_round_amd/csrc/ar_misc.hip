@@ -411,12 +411,10 @@ extern "C" int ar_pack_awq(const void* Wq, const void* scale, const float* zp_te
     if (gs <= 0 || in_f % gs || out_f % 8 || out_f <= 0 || in_f <= 0) return AR_ERR_UNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
     dim3 grid((unsigned)((in_f + kTPB - 1) / kTPB), (unsigned)(out_f / 8));
-    switch (w_dt) {
-        case AR_DT_BF16: hipLaunchKernelGGL(k_pack_awq<AR_DT_BF16>, grid, kTPB, 0, st, Wq, scale, zp_tensor, zp_scalar, out_f, in_f, gs, s_dt, qweight); break;
-        case AR_DT_F16: hipLaunchKernelGGL(k_pack_awq<AR_DT_F16>, grid, kTPB, 0, st, Wq, scale, zp_tensor, zp_scalar, out_f, in_f, gs, s_dt, qweight); break;
-        case AR_DT_F32: hipLaunchKernelGGL(k_pack_awq<AR_DT_F32>, grid, kTPB, 0, st, Wq, scale, zp_tensor, zp_scalar, out_f, in_f, gs, s_dt, qweight); break;
-        default: return AR_ERR_UNSUPPORTED;
-    }
+    const bool known = dispatch_dt(w_dt, [&](auto dt) {
+        hipLaunchKernelGGL(k_pack_awq<decltype(dt)::value>, grid, kTPB, 0, st, Wq, scale, zp_tensor, zp_scalar, out_f, in_f, gs, s_dt, qweight);
+    });
+    if (!known) return AR_ERR_UNSUPPORTED;
     int rc = launch_status();
     if (rc) return rc;
     const int64_t n_groups = in_f / gs;
@@ -447,12 +445,10 @@ extern "C" int ar_mse_loss_fwd_bwd(const void* pred, const void* ref, void* dpre
     const int grid = (int)(want < 1 ? 1 : (want > kMseMaxBlocks ? kMseMaxBlocks : want));
     const float alpha = (float)(2.0 / (double)n);
     double* partials = (double*)workspace;
-    switch (act_dt) {
-        case AR_DT_BF16: hipLaunchKernelGGL(k_mse_stage1<AR_DT_BF16>, grid, kTPB, 0, st, pred, ref, dpred, partials, n, alpha, grad_scale, token_mask, row_len); break;
-        case AR_DT_F16: hipLaunchKernelGGL(k_mse_stage1<AR_DT_F16>, grid, kTPB, 0, st, pred, ref, dpred, partials, n, alpha, grad_scale, token_mask, row_len); break;
-        case AR_DT_F32: hipLaunchKernelGGL(k_mse_stage1<AR_DT_F32>, grid, kTPB, 0, st, pred, ref, dpred, partials, n, alpha, grad_scale, token_mask, row_len); break;
-        default: return AR_ERR_UNSUPPORTED;
-    }
+    const bool known = dispatch_dt(act_dt, [&](auto dt) {
+        hipLaunchKernelGGL(k_mse_stage1<decltype(dt)::value>, grid, kTPB, 0, st, pred, ref, dpred, partials, n, alpha, grad_scale, token_mask, row_len);
+    });
+    if (!known) return AR_ERR_UNSUPPORTED;
     int rc = launch_status();
     if (rc) return rc;
     hipLaunchKernelGGL(k_mse_stage2, 1, kTPB, 0, st, partials, grid, n, loss_out, loss_accum, accum_scale);
@@ -538,12 +534,10 @@ extern "C" int ar_pack_int(const void* Wq, const void* scale, const float* zp_te
     hipStream_t st = (hipStream_t)stream;
     const int64_t n_groups = (in_f + gs - 1) / gs;
     dim3 grid((unsigned)((out_f + kTPB - 1) / kTPB), (unsigned)(in_f / 32));
-    switch (w_dt) {
-        case AR_DT_BF16: hipLaunchKernelGGL(k_pack_qweight<AR_DT_BF16>, grid, kTPB, 0, st, Wq, scale, zp_tensor, zp_scalar, out_f, in_f, gs, bits, s_dt, qweight); break;
-        case AR_DT_F16: hipLaunchKernelGGL(k_pack_qweight<AR_DT_F16>, grid, kTPB, 0, st, Wq, scale, zp_tensor, zp_scalar, out_f, in_f, gs, bits, s_dt, qweight); break;
-        case AR_DT_F32: hipLaunchKernelGGL(k_pack_qweight<AR_DT_F32>, grid, kTPB, 0, st, Wq, scale, zp_tensor, zp_scalar, out_f, in_f, gs, bits, s_dt, qweight); break;
-        default: return AR_ERR_UNSUPPORTED;
-    }
+    const bool known = dispatch_dt(w_dt, [&](auto dt) {
+        hipLaunchKernelGGL(k_pack_qweight<decltype(dt)::value>, grid, kTPB, 0, st, Wq, scale, zp_tensor, zp_scalar, out_f, in_f, gs, bits, s_dt, qweight);
+    });
+    if (!known) return AR_ERR_UNSUPPORTED;
     int rc = launch_status();
     if (rc) return rc;
     int64_t work = n_groups * out_f;

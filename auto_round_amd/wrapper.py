@@ -285,7 +285,7 @@ class BlockArena:
         self.wq_fresh = False       # Wq corresponds to the current parameters
         self.kind = "mx" if is_mx_fp(self.data_type) else ("nv" if is_nv_fp(self.data_type) else "int")
         cpg = self.gs // 8
-        self.tiled = cpg <= 64 and (cpg & (cpg - 1)) == 0     # lane-group kernels; otherwise one wave per group
+        self.lane_groups = cpg <= 64 and (cpg & (cpg - 1)) == 0     # lane-group kernels; otherwise one wave per group
         self.mode = {"int": -1, "mx": 0, "nv": 1}[self.kind]
         # `sym` as the kernels take it: 0 asym, 1 sym, 2 (AR_SYM_INIT) sym with the searched init scale in the wmax slot
         self.sym_code = 2 if (self.optimized and self.kind == "int") else int(bool(self.sym))
@@ -527,8 +527,8 @@ class BlockArena:
                              bits=self.bits, sym=self.sym_code, lr_v=lr_v, lr_mm=lr_mm, tune_minmax=self.tune_minmax,
                              scale_dtype=self.scale_dtype, q_thresh=self.q_thresh, bounds=self.bounds,
                              snapshot_flag=snapshot_flag, best_V=self.best_V, best_min=self.best_min,
-                             best_max=self.best_max, Wq_next=self.Wq if (fuse_next_fwd and self.tiled) else None)
-        self.wq_fresh = bool(fuse_next_fwd and self.tiled)
+                             best_max=self.best_max, Wq_next=self.Wq if (fuse_next_fwd and self.lane_groups) else None)
+        self.wq_fresh = bool(fuse_next_fwd and self.lane_groups)
         for lyr in self.layers:
             lyr._dw_accum[0] = False
 

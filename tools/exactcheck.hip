@@ -10,8 +10,6 @@
 #include <stdio.h>
 #include <string.h>
 
-#define AR_FASTDIV 1
-#define AR_HW_BF16 1
 #include "../auto_round_amd/csrc/ar_common.hpp"
 using namespace ar;
 
