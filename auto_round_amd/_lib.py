@@ -17,7 +17,7 @@ CSRC = os.path.join(_PKG, "csrc")
 
 AR_DT_BF16, AR_DT_F16, AR_DT_F32 = 0, 1, 2
 AR_ERR_UNSUPPORTED = -1
-ABI_VERSION = 28
+ABI_VERSION = 29
 
 
 class Mi355xLibraryError(RuntimeError):
@@ -89,6 +89,9 @@ SIGNATURES = {
     "ar_attn_fwd_exact": (c_int, [P, P, P, P, P, L, L, L, L, L, F, F, F, L, L, L, L, L, L, L, L, L, L, L, P]),
     "ar_attn_bwd_exact_workspace_bytes": (c_int64, [L, L, L]),
     "ar_attn_bwd_exact": (c_int, [P, P, P, P, P, P, P, P, P, L, L, L, L, L, F, F, F, L] + [L] * 18 + [P, L, P]),
+    "ar_attn_bwd_exact_grouped_workspace_bytes": (c_int64, [L, L, L, L]),
+    "ar_attn_bwd_exact_grouped": (c_int, [P, P, P, P, P, P, P, P, P, L, L, L, L, L, F, F, F, L] + [L] * 18 + [P, L, P]),
+    "ar_attn_bwd_grouped_run": (c_int, [L, L, L, P, P]),
     "ar_attn_bwd_workspace_bytes": (c_int64, [L, L, L]),
     "ar_attn_bwd": (c_int, [P, P, P, P, P, P, P, P, P, L, L, L, L, F, I, L, L, L, L, L, L, L, L, P, L, P]),
     "ar_attn_bwd_masked": (c_int, [P, P, P, P, P, P, P, P, P, L, L, L, L, F, F, F, L, L, L, L, L, L, L, L, L, P, L, P]),

@@ -38,6 +38,7 @@
 // repeat_kv only copies, the product reads the un-repeated rows.
 // Built with -ffp-contract=off like the rest of the library: every fma below is written out.
 #include "ar_common.hpp"
+#include "ar_attn_sched.hpp"
 #include <cstring>
 #include <type_traits>
 
@@ -463,12 +464,40 @@ namespace ar {
 //     tools/gpu/r06_mfma_kslot_probe.hip);
 //   * dq = sm_scale * acc, dk = sm_scale * acc, dv = acc, rounded to bf16.
 // The kernels are csrc/ar_attn_bwd.hip's (own row on the lane, two resident b-operands, two streamed tensors through LDS-DMA) with
-// that arithmetic; dK / dV are written per QUERY head (the caller sums the kv_rep heads of a group as autograd's expand does).
+// that arithmetic; dK / dV are written per QUERY head (the caller sums the kv_rep heads of a group as autograd's expand does) by
+// ar_attn_bwd_exact, and per KEY head by ar_attn_bwd_exact_grouped, whose key-side kernel sums the group itself:
+//
+// The PERSISTENT key side (k_xattn_bwd<1, 4, 128, 3, 1, GRP = 1 | 2>; head size 128).  The one-shot key-side kernel runs one workgroup
+// per CU (one wave per SIMD with the whole register file), 16 of them one after another at Llama-3-8B's minibatch, and nothing is
+// co-resident to hide a workgroup's set-up (2 S floats staged into LDS by a dependent load-store loop, 16 scattered 16-byte K / V loads
+// per lane, a barrier, the wait for the first LDS-DMA) and tear-down (64 eight-byte stores per lane); the kv_rep workgroups of a group
+// load the same K / V fragments.  The persistent form launches min(items, CUs) workgroups; each walks a fixed contiguous run of
+// (batch, key head, 128-key block) items (ar_attn_sched.hpp: computed from the workgroup's index alone, nothing is communicated
+// between workgroups) and, per item, the group's query heads in ascending order:
+//   * K / V fragments are loaded once per item, not once per query head;
+//   * the tile loop is the one-shot kernel's source (same order, same waits; the vectors are read at a run-time LDS offset), but the
+//     tiles of consecutive (item, head) units form one
+//     stream through the two tile buffers: the first tile of the next unit is fetched behind the last tile of the current one;
+//   * the L2 / delta vectors of a unit come by LDS-DMA (no registers) into one of two vector buffers, the next unit's behind the
+//     current unit's first tile;
+//   * dK / dV: every head's result is rounded to bf16 as the one-shot kernel stores it; the group's sum -- fp32 over those bf16
+//     numbers in the order of torch's `sum` over the expanded head axis, rounded once: four accumulators, head j into accumulator
+//     j % 4, then ((c0 + c1) + c2) + c3 -- for groups of up to 4 simply ascending heads from +0, for groups of 8 the pairs (j, j + 4)
+//     first (an instantiation of its own, GRP = 2).  The order was probed against torch's sum (profiles/attn_bwd_grouped_ab.json) and is held to autograd's bits by
+//     tests/test_gpu_attn_bwd_grouped.py (head-scaled addends, and exact cancellation between heads j and j + 4) -- it is formed by the
+//     lane that computed them and written once per KEY head,
+//     with the caller's token strides (dV lands in its column slice of the merged q|k|v gradient buffer).  Running fp32 sums in
+//     registers (128 more per lane) did not fit: 232 VGPRs + 160 AGPRs before, 256 + 256 and 480-668 bytes of scratch with them.  So
+//     the heads before the last park their bf16 results in a staging area private to the workgroup ((kv_rep - 1) x 64 KB, reused item
+//     after item: 192 KB per CU at kv_rep 4, more than the L2 holds for 32 CUs, so part of it lives in the Infinity Cache), and the
+//     last head's epilogue reads them back: 255 VGPRs + 219 AGPRs, no scratch (GRP = 2: 255 + 184).
+// Every reuse of an LDS buffer across units is argued where it happens (the loop at the end of k_xattn_bwd).
 
 struct XBwdArgs {
     const uint16_t* Q; const uint16_t* K; const uint16_t* V; const uint16_t* dO;
     const float* L2; const float* Dv;                              // [B, H, S] fp32: fl(lse * log2 e), delta
     uint16_t* dQ; uint16_t* dK; uint16_t* dV;                      // token-major [B, S, H, D] with token strides below
+    uint2* stage;                                                  // grouped key side only: workgroups x (kv_rep - 1) x 64 KB
     int B, S, H, kv_rep;
     int64_t q_bs, q_hs, q_ts, k_bs, k_hs, k_ts, v_bs, v_hs, v_ts, o_bs, o_hs, o_ts;      // element strides (batch, head, token); o = dO
     int64_t lddq, lddk, lddv;
@@ -510,10 +539,11 @@ __global__ __launch_bounds__(kTPB) void k_xattn_bwd_prep(const uint16_t* __restr
 }
 
 // MODE 0: dQ (own rows = queries; K / V tiles stream).  MODE 1: dK / dV (own rows = keys; Q / dO tiles stream); OUT: 3 = both,
-// 1 = dV only, 2 = dK only.  Launched: the key side always with OUT = 3 on 4 waves -- at head size 128 with OCC = 1, one wave per SIMD
+// 1 = dV only, 2 = dK only.  GRP: the persistent, group-summing key side (above).  Launched: the key side always with OUT = 3 on 4 waves
+// -- at head size 128 with OCC = 1, one wave per SIMD
 // and the whole register file (the key side as two kernels, OUT = 1 and 2 at OCC = 2, and the 8-wave key side were measured slower,
 // profiles/r06_attn_exact_waves_ab.json, and are not instantiated any more); the query side on 4 waves, or 8 at head size 128.
-template <int MODE, int WAVES, int AD, int OUT = 3, int OCC = 2>
+template <int MODE, int WAVES, int AD, int OUT = 3, int OCC = 2, int GRP = 0>
 __global__ __launch_bounds__(64 * WAVES, OCC) void k_xattn_bwd(XBwdArgs a) {
     constexpr bool NEED_S1 = MODE == 0 || (OUT & 2);
     constexpr bool NEED_A0 = MODE == 0 || (OUT & 2);
@@ -534,43 +564,52 @@ __global__ __launch_bounds__(64 * WAVES, OCC) void k_xattn_bwd(XBwdArgs a) {
                   "head size 128: the key side as two kernels (register budget), or one wave per SIMD with the whole register file");
     static_assert(MODE == 0 ? (OUT == 3 && OCC == 2 && (WAVES == 4 || (WAVES == 8 && AD == 128))) : (MODE == 1 && WAVES == 4 && OUT == 3 && OCC == (AD == 128 ? 1 : 2)),
                   "the instantiations ar_attn_bwd_exact launches");
+    static_assert(!GRP || (MODE == 1 && AD == 128), "the persistent, group-summing form exists for the key side at head size 128");
     extern __shared__ __attribute__((aligned(1024))) uint8_t lds[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int h = lane >> 5, lq = lane & 31;
     const int n_ob = a.S / AQ;
-    int ob, bh;
-    xattn_map((int)blockIdx.x, n_ob, a.B, a.H, a.kv_rep, MODE == 0, ob, bh);
-    const int b = bh / a.H, head = bh % a.H, kvh = head / a.kv_rep;
-    const int o0 = ob * AQ;
-    const int myrow = o0 + 32 * wave + lq;
     const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint8_t*)lds;
     constexpr int VEC_OFF = 2 * ABUF;
-
-    const uint16_t* Qh = a.Q + (int64_t)b * a.q_bs + (int64_t)head * a.q_hs;
-    const uint16_t* Kh = a.K + (int64_t)b * a.k_bs + (int64_t)kvh * a.k_hs;
-    const uint16_t* Vh = a.V + (int64_t)b * a.v_bs + (int64_t)kvh * a.v_hs;
-    const uint16_t* Oh = a.dO + (int64_t)b * a.o_bs + (int64_t)head * a.o_hs;
     const int64_t ld0 = MODE == 0 ? a.k_ts : a.q_ts, ld1 = MODE == 0 ? a.v_ts : a.o_ts;
-    const uint16_t* R0b = MODE == 0 ? Kh : Qh;
-    const uint16_t* R1b = MODE == 0 ? Vh : Oh;
     const int64_t lb0 = MODE == 0 ? a.q_ts : a.k_ts, lb1 = MODE == 0 ? a.o_ts : a.v_ts;
-    const uint16_t* B0b = MODE == 0 ? Qh : Kh;
-    const uint16_t* B1b = MODE == 0 ? Oh : Vh;
+    // what one unit of work is about.  One-shot form: fixed per workgroup.  GRP: (b, kvh, o0, myrow, bf0, bf1) change per item, (head, R0b,
+    // R1b, vec_off) per query head of the item's group.
+    int b, head, kvh, o0, myrow;
+    int vec_off = VEC_OFF;                                 // the L2 / delta vectors of the unit in LDS (GRP: two buffers, alternating)
+    const uint16_t* R0b;
+    const uint16_t* R1b;
     xbf16x8_t bf0[NKS], bf1[NKS];
-#pragma unroll
-    for (int ks = 0; ks < NKS; ++ks) {
-        bf0[ks] = __builtin_bit_cast(xbf16x8_t, *reinterpret_cast<const uint4*>(B0b + (int64_t)myrow * lb0 + 16 * ks + 8 * h));
-        if (NEED_S1) bf1[ks] = __builtin_bit_cast(xbf16x8_t, *reinterpret_cast<const uint4*>(B1b + (int64_t)myrow * lb1 + 16 * ks + 8 * h));
-    }
-    const float* L2row = a.L2 + ((int64_t)b * a.H + head) * a.S;
-    const float* Dvrow = a.Dv + ((int64_t)b * a.H + head) * a.S;
     float myL2 = 0.f, myD = 0.f;
-    if (MODE == 0) { myL2 = L2row[myrow]; myD = Dvrow[myrow]; }
-    if (MODE == 1) {
-        float* vL = reinterpret_cast<float*>(lds + VEC_OFF);
-        float* vD = vL + a.S;
-        for (int i = tid; i < a.S; i += 64 * WAVES) { vL[i] = L2row[i]; vD[i] = Dvrow[i]; }
+    auto load_own = [&](const uint16_t* B0b, const uint16_t* B1b) {
+#pragma unroll
+        for (int ks = 0; ks < NKS; ++ks) {
+            bf0[ks] = __builtin_bit_cast(xbf16x8_t, *reinterpret_cast<const uint4*>(B0b + (int64_t)myrow * lb0 + 16 * ks + 8 * h));
+            if (NEED_S1) bf1[ks] = __builtin_bit_cast(xbf16x8_t, *reinterpret_cast<const uint4*>(B1b + (int64_t)myrow * lb1 + 16 * ks + 8 * h));
+        }
+    };
+    if constexpr (!GRP) {
+        int ob, bh;
+        xattn_map((int)blockIdx.x, n_ob, a.B, a.H, a.kv_rep, MODE == 0, ob, bh);
+        b = bh / a.H; head = bh % a.H; kvh = head / a.kv_rep;
+        o0 = ob * AQ;
+        myrow = o0 + 32 * wave + lq;
+        const uint16_t* Qh = a.Q + (int64_t)b * a.q_bs + (int64_t)head * a.q_hs;
+        const uint16_t* Kh = a.K + (int64_t)b * a.k_bs + (int64_t)kvh * a.k_hs;
+        const uint16_t* Vh = a.V + (int64_t)b * a.v_bs + (int64_t)kvh * a.v_hs;
+        const uint16_t* Oh = a.dO + (int64_t)b * a.o_bs + (int64_t)head * a.o_hs;
+        R0b = MODE == 0 ? Kh : Qh;
+        R1b = MODE == 0 ? Vh : Oh;
+        load_own(MODE == 0 ? Qh : Kh, MODE == 0 ? Oh : Vh);
+        const float* L2row = a.L2 + ((int64_t)b * a.H + head) * a.S;
+        const float* Dvrow = a.Dv + ((int64_t)b * a.H + head) * a.S;
+        if (MODE == 0) { myL2 = L2row[myrow]; myD = Dvrow[myrow]; }
+        if (MODE == 1) {
+            float* vL = reinterpret_cast<float*>(lds + VEC_OFF);
+            float* vD = vL + a.S;
+            for (int i = tid; i < a.S; i += 64 * WAVES) { vL[i] = L2row[i]; vD[i] = Dvrow[i]; }
+        }
     }
     // MODE 1: the library's non-fused element -- accumulator register 15 of its key block = keys 27 and 31 of every 32
     const bool quirk = MODE == 1 && (lq == 27 || lq == 31);
@@ -584,15 +623,16 @@ __global__ __launch_bounds__(64 * WAVES, OCC) void k_xattn_bwd(XBwdArgs a) {
         doff0[p] = (uint32_t)(r * ld0 + (pchunk ^ xattn_swz<AD>(r)) * 8);
         doff1[p] = (uint32_t)(r * ld1 + (pchunk ^ xattn_swz<AD>(r)) * 8);
     }
-    auto issue_tile = [&](int t, int buf) {
+    auto issue_tile_of = [&](const uint16_t* S0, const uint16_t* S1, int t, int buf) {
 #pragma unroll
         for (int j = 0; j < 2 * NP; ++j) {
             const int p = j % NP;
-            const uint16_t* T = (j < NP ? R0b + (int64_t)t * XK * ld0 + doff0[p] : R1b + (int64_t)t * XK * ld1 + doff1[p]);
+            const uint16_t* T = (j < NP ? S0 + (int64_t)t * XK * ld0 + doff0[p] : S1 + (int64_t)t * XK * ld1 + doff1[p]);
             const uint32_t dst = lds0 + buf * ABUF + (j < NP ? 0 : ATILE) + (RPW * wave + RPI * p) * AROW;
             __builtin_amdgcn_global_load_lds((const void*)T, (__attribute__((address_space(3))) void*)(uintptr_t)dst, 16, 0, 0);
         }
     };
+    auto issue_tile = [&](int t, int buf) { issue_tile_of(R0b, R1b, t, buf); };
 
     uint32_t rA[NKS];
 #pragma unroll
@@ -691,7 +731,7 @@ __global__ __launch_bounds__(64 * WAVES, OCC) void k_xattn_bwd(XBwdArgs a) {
                     s1[r] = p * dd;
                 }
             } else {
-                const float* vL = reinterpret_cast<const float*>(lds + VEC_OFF);
+                const float* vL = reinterpret_cast<const float*>(lds + vec_off);
                 const float* vD = vL + a.S;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
@@ -754,23 +794,22 @@ __global__ __launch_bounds__(64 * WAVES, OCC) void k_xattn_bwd(XBwdArgs a) {
     };
 
     const int t_end = a.S / XK;
-    __syncthreads();
-    issue_tile(0, 0);
-    for (int t = 0; t < t_end; t += 2) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        issue_tile(t + 1, 1);
-        tile(std::integral_constant<int, 0>{}, t * XK);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        if (t + 2 < t_end) issue_tile(t + 2, 0);
-        tile(std::integral_constant<int, 1>{}, (t + 1) * XK);
+    if constexpr (!GRP) {
+        __syncthreads();
+        issue_tile(0, 0);
+        for (int t = 0; t < t_end; t += 2) {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
+            issue_tile(t + 1, 1);
+            tile(std::integral_constant<int, 0>{}, t * XK);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
+            if (t + 2 < t_end) issue_tile(t + 2, 0);
+            tile(std::integral_constant<int, 1>{}, (t + 1) * XK);
+        }
     }
-#undef XB_RREAD
-#undef XB_TREAD
-#undef XB_PIN
-    auto store = [&](uint16_t* base, int64_t ld, const xf32x16_t (&acc)[ND], float mul, bool scaled) {
-        uint16_t* orow = base + ((int64_t)b * a.S + myrow) * ld + head * AD;
+    auto store = [&](uint16_t* base, int64_t ld, int hcol, const xf32x16_t (&acc)[ND], float mul, bool scaled) {
+        uint16_t* orow = base + ((int64_t)b * a.S + myrow) * ld + hcol * AD;
 #pragma unroll
         for (int dt = 0; dt < ND; ++dt)
 #pragma unroll
@@ -786,11 +825,216 @@ __global__ __launch_bounds__(64 * WAVES, OCC) void k_xattn_bwd(XBwdArgs a) {
                 *reinterpret_cast<uint2*>(orow + 32 * dt + 8 * j + 4 * h) = w;
             }
     };
-    if (MODE == 0) store(a.dQ, a.lddq, acc0, a.sm_scale, true);
-    else {
-        if (NEED_A0) store(a.dK, a.lddk, acc0, a.sm_scale, true);
-        if (NEED_A1) store(a.dV, a.lddv, acc1, 1.0f, false);
+    if constexpr (!GRP) {
+        if (MODE == 0) store(a.dQ, a.lddq, head, acc0, a.sm_scale, true);
+        else {
+            if (NEED_A0) store(a.dK, a.lddk, head, acc0, a.sm_scale, true);
+            if (NEED_A1) store(a.dV, a.lddv, head, acc1, 1.0f, false);
+        }
+    } else {
+        // ---- the persistent, group-summing form: one workgroup per CU walks a fixed run of items (ar_attn_sched.hpp), and per item the
+        // kv_rep query heads of the key head's group in ascending order.  A UNIT is one (item, query head): the one-shot kernel's whole
+        // tile loop.  The tiles of all units form ONE stream through the two tile buffers (S / 64 is even, so every unit starts in
+        // buffer 0), and the units' L2 / delta vectors alternate between two vector buffers.  dK / dV of the group are summed by the lane
+        // that computed them: each head's result is rounded to bf16 exactly as the one-shot kernel stores it; all heads but the last
+        // park those bf16 numbers in a staging area private to the workgroup (running fp32 sums in registers -- 128 more per lane --
+        // do not fit beside the tile loop's 392: the compiler spilled to scratch); after the last head the lane adds them in fp32 in
+        // the order of torch's sum over the expanded head axis (sum_group / sum_group8), rounds once and writes the KEY head's dK / dV: [B, S, H / kv_rep, D] with token strides lddk / lddv.
+        // kv_rep == 1: no sum, the head's result is written as it is.
+        const int rep = a.kv_rep, hk = a.H / rep;
+        const int n_runs = (int)gridDim.x;
+        int first, count;
+        xattn_group_run(xattn_group_run_of_block((int)blockIdx.x, n_runs), n_runs, a.B * hk * n_ob, first, count);
+        const int vec_bytes = 2 * a.S * (int)sizeof(float);
+        auto set_item = [&](int item) {                                   // the item's own rows: K / V fragments, loaded ONCE per group
+            const int g = item / n_ob;
+            b = g / hk; kvh = g % hk;
+            o0 = (item % n_ob) * AQ;
+            myrow = o0 + 32 * wave + lq;
+            load_own(a.K + (int64_t)b * a.k_bs + (int64_t)kvh * a.k_hs, a.V + (int64_t)b * a.v_bs + (int64_t)kvh * a.v_hs);
+        };
+        // the L2 / delta rows of (batch hb, query head hh) into vector buffer vb by LDS-DMA, 64 floats per instruction: no registers, and
+        // counted by vmcnt like the tiles, so the tile loop's own `vmcnt(0)` + barrier publishes them
+        auto issue_vec = [&](int hb, int hh, int vb) {
+            const float* L = a.L2 + ((int64_t)hb * a.H + hh) * a.S + lane;
+            const float* Dl = a.Dv + ((int64_t)hb * a.H + hh) * a.S + lane;
+            const uint32_t dst = lds0 + VEC_OFF + vb * vec_bytes;
+            for (int c = wave; c < a.S / 64; c += WAVES) {
+                __builtin_amdgcn_global_load_lds((const void*)(L + 64 * c), (__attribute__((address_space(3))) void*)(uintptr_t)(dst + 256 * c), 4, 0, 0);
+                __builtin_amdgcn_global_load_lds((const void*)(Dl + 64 * c), (__attribute__((address_space(3))) void*)(uintptr_t)(dst + 4 * a.S + 256 * c), 4, 0, 0);
+            }
+        };
+        // head j < kv_rep - 1 of the item parks its rounded results here: (kv_rep - 1) x 64 KB per workgroup; a lane's 128 bytes per
+        // (head, tensor) are contiguous (one base address, 16-byte accesses), and every lane reads back only what it wrote itself
+        constexpr int STAGE_T = 64 * WAVES * ND * 2;                       // uint4 per (head, tensor)
+        // (GRP == 2, groups of 8: all 8 heads park)
+        uint4* stage = reinterpret_cast<uint4*>(a.stage) + (int64_t)blockIdx.x * (GRP == 2 ? 8 : rep - 1) * (2 * STAGE_T) + tid * (ND * 2);
+        auto rounded = [&](const xf32x16_t (&acc)[ND], int dt, int j2, float mul, bool scaled) {      // rows 8 j2 .. 8 j2 + 7, as `store` rounds
+            uint4 w;
+            if (scaled) {
+                w.x = pack_bf16x2(mul * acc[dt][8 * j2 + 0], mul * acc[dt][8 * j2 + 1]);
+                w.y = pack_bf16x2(mul * acc[dt][8 * j2 + 2], mul * acc[dt][8 * j2 + 3]);
+                w.z = pack_bf16x2(mul * acc[dt][8 * j2 + 4], mul * acc[dt][8 * j2 + 5]);
+                w.w = pack_bf16x2(mul * acc[dt][8 * j2 + 6], mul * acc[dt][8 * j2 + 7]);
+            } else {
+                w.x = pack_bf16x2(acc[dt][8 * j2 + 0], acc[dt][8 * j2 + 1]);
+                w.y = pack_bf16x2(acc[dt][8 * j2 + 2], acc[dt][8 * j2 + 3]);
+                w.z = pack_bf16x2(acc[dt][8 * j2 + 4], acc[dt][8 * j2 + 5]);
+                w.w = pack_bf16x2(acc[dt][8 * j2 + 6], acc[dt][8 * j2 + 7]);
+            }
+            return w;
+        };
+        auto stage_head = [&](int j, int tensor, const xf32x16_t (&acc)[ND], float mul, bool scaled) {
+            uint4* sp = stage + (j * 2 + tensor) * STAGE_T;
+#pragma unroll
+            for (int q = 0; q < ND * 2; ++q) sp[q] = rounded(acc, q >> 1, q & 1, mul, scaled);
+        };
+        // the group's sum for one tensor, groups of up to 4: ((((+0 + a0) + a1) + a2) + a3) in fp32 over the heads' bf16 results, rounded
+        // once -- what the four accumulators of torch's sum over the expanded head axis (head j into accumulator j % 4, then
+        // ((c0 + c1) + c2) + c3) amount to for up to four addends.  a0 .. come from the staging area (all loads of the tensor in flight
+        // at once), the last head's from the accumulators.  A head the group does not have counts as +0, which changes no sum that
+        // started from +0.
+        auto sum_group = [&](uint16_t* base, int64_t ld, int tensor, const xf32x16_t (&acc)[ND], float mul, bool scaled) {
+            constexpr int MAXP = 3;                                        // parked heads at the most
+            uint4 st[MAXP][ND * 2];
+#pragma unroll
+            for (int jh = 0; jh < MAXP; ++jh) {
+                if (jh < rep - 1) {
+                    const uint4* sp = stage + (jh * 2 + tensor) * STAGE_T;
+#pragma unroll
+                    for (int q = 0; q < ND * 2; ++q) st[jh][q] = sp[q];
+                } else {
+#pragma unroll
+                    for (int q = 0; q < ND * 2; ++q) st[jh][q] = uint4{0u, 0u, 0u, 0u};
+                }
+            }
+            uint16_t* orow = base + ((int64_t)b * a.S + myrow) * ld + kvh * AD;
+#pragma unroll
+            for (int q = 0; q < ND * 2; ++q) {
+                float c[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+                auto add = [&](uint4 w) {
+                    const uint32_t u[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        c[2 * e] = c[2 * e] + __uint_as_float(u[e] << 16);
+                        c[2 * e + 1] = c[2 * e + 1] + __uint_as_float(u[e] & 0xffff0000u);
+                    }
+                };
+#pragma unroll
+                for (int jh = 0; jh < MAXP; ++jh) add(st[jh][q]);
+                add(rounded(acc, q >> 1, q & 1, mul, scaled));
+                uint2 w0, w1;
+                w0.x = pack_bf16x2(c[0], c[1]); w0.y = pack_bf16x2(c[2], c[3]);
+                w1.x = pack_bf16x2(c[4], c[5]); w1.y = pack_bf16x2(c[6], c[7]);
+                *reinterpret_cast<uint2*>(orow + 32 * (q >> 1) + 16 * (q & 1) + 4 * h) = w0;
+                *reinterpret_cast<uint2*>(orow + 32 * (q >> 1) + 16 * (q & 1) + 8 + 4 * h) = w1;
+            }
+        };
+        // groups of exactly 8 (GRP == 2): torch's order pairs heads (j, j + 4) first.  Seven parked heads of a tensor in flight beside the
+        // accumulators do not fit the register file, so the last head parks its results too (slot 7), and a rolled loop takes one 16-byte
+        // piece of all 8 heads at a time: 32 registers, at the price of 16 dependent round trips to the L2 per item.
+        auto sum_group8 = [&]() {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");              // the lane's own stores of slot 7, before it reads them back
+            const int64_t row = (int64_t)b * a.S + myrow;
+#pragma unroll 1
+            for (int tq = 0; tq < 2 * ND * 2; ++tq) {
+                const int tensor = tq / (ND * 2), q = tq % (ND * 2);
+                uint4 w[8];
+#pragma unroll
+                for (int jh = 0; jh < 8; ++jh) w[jh] = stage[(jh * 2 + tensor) * STAGE_T + q];
+                float c[4][8];
+#pragma unroll
+                for (int l = 0; l < 4; ++l) {
+                    const uint32_t u0[4] = {w[l].x, w[l].y, w[l].z, w[l].w}, u1[4] = {w[l + 4].x, w[l + 4].y, w[l + 4].z, w[l + 4].w};
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        c[l][2 * e] = (0.f + __uint_as_float(u0[e] << 16)) + __uint_as_float(u1[e] << 16);
+                        c[l][2 * e + 1] = (0.f + __uint_as_float(u0[e] & 0xffff0000u)) + __uint_as_float(u1[e] & 0xffff0000u);
+                    }
+                }
+                float t8[8];
+#pragma unroll
+                for (int e = 0; e < 8; ++e) t8[e] = ((c[0][e] + c[1][e]) + c[2][e]) + c[3][e];
+                uint2 w0, w1;
+                w0.x = pack_bf16x2(t8[0], t8[1]); w0.y = pack_bf16x2(t8[2], t8[3]);
+                w1.x = pack_bf16x2(t8[4], t8[5]); w1.y = pack_bf16x2(t8[6], t8[7]);
+                uint16_t* orow = (tensor ? a.dV + row * a.lddv : a.dK + row * a.lddk) + kvh * AD + 32 * (q >> 1) + 16 * (q & 1) + 4 * h;
+                *reinterpret_cast<uint2*>(orow) = w0;
+                *reinterpret_cast<uint2*>(orow + 8) = w1;
+            }
+        };
+        set_item(first);
+        head = kvh * rep;
+        R0b = a.Q + (int64_t)b * a.q_bs + (int64_t)head * a.q_hs;
+        R1b = a.dO + (int64_t)b * a.o_bs + (int64_t)head * a.o_hs;
+        int vb = 0;
+        // the first unit's vectors and first tile: nothing has touched LDS yet, and the first `vmcnt(0)` + barrier below publishes both
+        issue_vec(b, head, 0);
+        issue_tile(0, 0);
+        for (int it = 0; it < count; ++it)
+            for (int j = 0; j < rep; ++j) {
+                const bool more = j + 1 < rep || it + 1 < count;         // a unit follows: the next head, or the next item's first head
+                int nb = b, nhead = head + 1;
+                if (j + 1 == rep && more) {
+                    const int g = (first + it + 1) / n_ob;
+                    nb = g / hk; nhead = (g % hk) * rep;
+                }
+                const uint16_t* N0 = a.Q + (int64_t)nb * a.q_bs + (int64_t)nhead * a.q_hs;
+                const uint16_t* N1 = a.dO + (int64_t)nb * a.o_bs + (int64_t)nhead * a.o_hs;
+                for (int t = 0; t < t_end; t += 2) {
+                    // `vmcnt(0)`: this wave's DMA of tile t (and, at t == 0 of the first unit, of the unit's vectors; later units' vectors
+                    // landed before tile 1 of the unit before) has landed, and so have an item boundary's stores and K / V loads.  The
+                    // barrier: every wave's has, and every wave has finished tile t - 1 -- at t == 0 the LAST tile of the unit before,
+                    // which read tile buffer 1 and vector buffer vb ^ 1 for the last time.
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                    __builtin_amdgcn_s_barrier();
+                    issue_tile(t + 1, 1);                                  // buffer 1 is free (above)
+                    if (t == 0 && more) issue_vec(nb, nhead, vb ^ 1);     // so is vector buffer vb ^ 1; published by the next barrier
+                    tile(std::integral_constant<int, 0>{}, t * XK);
+                    // `vmcnt(0)` + barrier: tile t + 1 (and the next unit's vectors) landed for every wave, every wave finished tile t
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                    __builtin_amdgcn_s_barrier();
+                    // buffer 0 is free (every wave finished tile t): this unit's tile t + 2, or the NEXT unit's first tile, whose latency
+                    // hides behind this unit's last tile; the next unit's first `vmcnt(0)` + barrier publishes it
+                    if (t + 2 < t_end) issue_tile(t + 2, 0);
+                    else if (more) issue_tile_of(N0, N1, 0, 0);
+                    tile(std::integral_constant<int, 1>{}, (t + 1) * XK);
+                }
+                // ---- head boundary: registers only (the next unit's first tile is in flight)
+                if (rep == 1) {
+                    store(a.dK, a.lddk, kvh, acc0, a.sm_scale, true);
+                    store(a.dV, a.lddv, kvh, acc1, 1.0f, false);
+                } else if (j + 1 < rep) {
+                    // the stores are complete long before the group's last head reads them back: every tile of the next unit waits for
+                    // `vmcnt(0)`; same lane, same addresses, and the CU's vector cache is coherent for its own stores
+                    stage_head(j, 0, acc0, a.sm_scale, true);
+                    stage_head(j, 1, acc1, 1.0f, false);
+                } else {
+                    if constexpr (GRP == 2) {
+                        stage_head(7, 0, acc0, a.sm_scale, true);
+                        stage_head(7, 1, acc1, 1.0f, false);
+                        sum_group8();
+                    } else {
+                        sum_group(a.dK, a.lddk, 0, acc0, a.sm_scale, true);
+                        sum_group(a.dV, a.lddv, 1, acc1, 1.0f, false);
+                    }
+                }
+#pragma unroll
+                for (int dt = 0; dt < ND; ++dt)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) { acc0[dt][r] = 0.f; acc1[dt][r] = 0.f; }
+                // item boundary: the next item's rows (b, kvh, o0, myrow) and K / V fragments -- after the stores above used the old ones.
+                // The loads are waited for by the next unit's first `vmcnt(0)`; LDS is not involved.
+                if (j + 1 == rep && more) set_item(first + it + 1);
+                head = nhead;
+                R0b = N0; R1b = N1;
+                vb ^= 1;
+                vec_off = VEC_OFF + vb * vec_bytes;
+            }
     }
+#undef XB_RREAD
+#undef XB_TREAD
+#undef XB_PIN
 }
 
 
@@ -798,28 +1042,41 @@ __global__ __launch_bounds__(64 * WAVES, OCC) void k_xattn_bwd(XBwdArgs a) {
 
 extern "C" int64_t ar_attn_bwd_exact_workspace_bytes(int64_t B, int64_t S, int64_t H) { return 2 * B * S * H * (int64_t)sizeof(float); }
 
-extern "C" int ar_attn_bwd_exact(const void* Q, const void* K, const void* V, const void* O, const void* dO, const float* LSE, void* dQ, void* dK,
-                                 void* dV, int64_t B, int64_t S, int64_t H, int64_t D, int64_t kv_rep, float scale, float bias_in,
-                                 float bias_out, int64_t valid_len, int64_t q_bs, int64_t q_hs, int64_t q_ts, int64_t k_bs, int64_t k_hs,
-                                 int64_t k_ts, int64_t v_bs, int64_t v_hs, int64_t v_ts, int64_t o_bs, int64_t o_hs, int64_t o_ts,
-                                 int64_t do_bs, int64_t do_hs, int64_t do_ts, int64_t lddq, int64_t lddk, int64_t lddv, void* workspace,
-                                 int64_t workspace_bytes, ar_stream_t stream) {
+// the grouped form: the persistent key-side kernel runs on XGRP_MAX_WG workgroups at the most, each with (kv_rep - 1) x 64 KB of staging
+constexpr int64_t XGRP_MAX_WG = 512, XGRP_STAGE = 2 * 128 * 128 * 2;
+extern "C" int64_t ar_attn_bwd_exact_grouped_workspace_bytes(int64_t B, int64_t S, int64_t H, int64_t kv_rep) {
+    if (B <= 0 || S <= 0 || H <= 0 || kv_rep < 1 || H % kv_rep) return 0;
+    const int64_t items = B * (H / kv_rep) * ((S + 127) / 128);
+    return ar_attn_bwd_exact_workspace_bytes(B, S, H) + (items < XGRP_MAX_WG ? items : XGRP_MAX_WG) * (kv_rep > 4 ? 8 : kv_rep - 1) * XGRP_STAGE;
+}
+
+// grouped: dK / dV per KEY head (width (H / kv_rep) * D), the group summed in the key-side kernel -- head size 128 and groups of up to 4 or of 8
+// (the orders of torch's sum the kernel restates: its header) only
+static int xattn_bwd_exact_launch(bool grouped, const void* Q, const void* K, const void* V, const void* O, const void* dO, const float* LSE,
+                                  void* dQ, void* dK, void* dV, int64_t B, int64_t S, int64_t H, int64_t D, int64_t kv_rep, float scale,
+                                  float bias_in, float bias_out, int64_t valid_len, int64_t q_bs, int64_t q_hs, int64_t q_ts, int64_t k_bs,
+                                  int64_t k_hs, int64_t k_ts, int64_t v_bs, int64_t v_hs, int64_t v_ts, int64_t o_bs, int64_t o_hs,
+                                  int64_t o_ts, int64_t do_bs, int64_t do_hs, int64_t do_ts, int64_t lddq, int64_t lddk, int64_t lddv,
+                                  void* workspace, int64_t workspace_bytes, ar_stream_t stream) {
     if ((D != 64 && D != 128) || S % 128 || S > 4096 || B <= 0 || H <= 0 || kv_rep < 1 || H % kv_rep) return AR_ERR_UNSUPPORTED;
-    if (!workspace || workspace_bytes < ar_attn_bwd_exact_workspace_bytes(B, S, H)) return AR_ERR_UNSUPPORTED;
+    if (grouped && (D != 128 || (kv_rep > 4 && kv_rep != 8))) return AR_ERR_UNSUPPORTED;
+    if (!workspace || ((uintptr_t)workspace & 15) ||
+        workspace_bytes < (grouped ? ar_attn_bwd_exact_grouped_workspace_bytes(B, S, H, kv_rep) : ar_attn_bwd_exact_workspace_bytes(B, S, H)))
+        return AR_ERR_UNSUPPORTED;
     if (!(bias_in == bias_in) || !(bias_out == bias_out) || fabsf(bias_in) > 1e4f || fabsf(bias_out) > 1e4f || valid_len < 1 || valid_len > S)
         return AR_ERR_UNSUPPORTED;
     {
         uint32_t u0, u1; memcpy(&u0, &bias_in, 4); memcpy(&u1, &bias_out, 4);
         if ((u0 | u1) & 0xffffu) return AR_ERR_UNSUPPORTED;
     }
-    const int64_t hd = H * D;
+    const int64_t hd = H * D, hkd = grouped ? hd / kv_rep : hd;
     if (lddq <= 0) lddq = hd;
-    if (lddk <= 0) lddk = hd;
-    if (lddv <= 0) lddv = hd;
+    if (lddk <= 0) lddk = hkd;
+    if (lddv <= 0) lddv = hkd;
     const int64_t st[18] = {q_bs, q_hs, q_ts, k_bs, k_hs, k_ts, v_bs, v_hs, v_ts, o_bs, o_hs, o_ts, do_bs, do_hs, do_ts, lddq, lddk, lddv};
     for (int i = 0; i < 18; ++i)
         if (st[i] < 0 || (st[i] % 8)) return AR_ERR_UNSUPPORTED;
-    if (lddq < hd || lddk < hd || lddv < hd) return AR_ERR_UNSUPPORTED;
+    if (lddq < hd || lddk < hkd || lddv < hkd) return AR_ERR_UNSUPPORTED;
     if (64 * q_ts > 0x7fffffffLL || 64 * k_ts > 0x7fffffffLL || 64 * v_ts > 0x7fffffffLL || 64 * do_ts > 0x7fffffffLL) return AR_ERR_UNSUPPORTED;
     if (((uintptr_t)Q | (uintptr_t)K | (uintptr_t)V | (uintptr_t)O | (uintptr_t)dO | (uintptr_t)dQ | (uintptr_t)dK | (uintptr_t)dV) & 15)
         return AR_ERR_UNSUPPORTED;
@@ -834,6 +1091,7 @@ extern "C" int ar_attn_bwd_exact(const void* Q, const void* K, const void* V, co
     XBwdArgs a;
     a.Q = (const uint16_t*)Q; a.K = (const uint16_t*)K; a.V = (const uint16_t*)V; a.dO = (const uint16_t*)dO;
     a.L2 = L2; a.Dv = Dv;
+    a.stage = (uint2*)(L2 + B * S * H);                    // (2 B S H floats: a multiple of 16 bytes, S % 128 == 0)
     a.dQ = (uint16_t*)dQ; a.dK = (uint16_t*)dK; a.dV = (uint16_t*)dV;
     a.B = (int)B; a.S = (int)S; a.H = (int)H; a.kv_rep = (int)kv_rep;
     a.q_bs = q_bs; a.q_hs = q_hs; a.q_ts = q_ts; a.k_bs = k_bs; a.k_hs = k_hs; a.k_ts = k_ts; a.v_bs = v_bs; a.v_hs = v_hs; a.v_ts = v_ts;
@@ -849,6 +1107,8 @@ extern "C" int ar_attn_bwd_exact(const void* Q, const void* K, const void* V, co
     static PerDeviceOnce attr;
     if (attr.first()) {
         (void)hipFuncSetAttribute((const void*)k_xattn_bwd<1, 4, 128, 3, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_T128 + VEC_MAX);
+        (void)hipFuncSetAttribute((const void*)k_xattn_bwd<1, 4, 128, 3, 1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_T128 + 2 * VEC_MAX);
+        (void)hipFuncSetAttribute((const void*)k_xattn_bwd<1, 4, 128, 3, 1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_T128 + 2 * VEC_MAX);
         (void)hipFuncSetAttribute((const void*)k_xattn_bwd<0, 8, 128>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_T128);
         (void)hipFuncSetAttribute((const void*)k_xattn_bwd<0, 4, 128>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_T128);
         (void)hipFuncSetAttribute((const void*)k_xattn_bwd<1, 4, 64>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_T + VEC_MAX);
@@ -857,7 +1117,19 @@ extern "C" int ar_attn_bwd_exact(const void* Q, const void* K, const void* V, co
     if (D == 128) {
         // dK and dV in ONE kernel (7 GEMM passes instead of 8): 4 waves, one wave per SIMD with the whole register file (accumulators in
         // the AGPRs) -- 3 % faster than the key side as two kernels; the query side on 8 waves where S allows
-        hipLaunchKernelGGL((k_xattn_bwd<1, 4, 128, 3, 1>), grid4, 256, LDS_T128 + vec, s, a);
+        if (grouped) {
+            // persistent: one workgroup per CU at the most, each with a fixed run of (batch, key head, key block) items
+            int dev = 0, n_cu = 0;
+            if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0)
+                return AR_ERR_UNSUPPORTED;
+            int64_t wgs = B * (H / kv_rep) * (S / 128);
+            if (wgs > n_cu) wgs = n_cu;
+            if (wgs > XGRP_MAX_WG) wgs = XGRP_MAX_WG;
+            // (groups of more than 4 sum in another order and in passes: an instantiation of their own, so neither pays the other's registers)
+            if (kv_rep > 4) hipLaunchKernelGGL((k_xattn_bwd<1, 4, 128, 3, 1, 2>), (int)wgs, 256, LDS_T128 + 2 * vec, s, a);
+            else hipLaunchKernelGGL((k_xattn_bwd<1, 4, 128, 3, 1, 1>), (int)wgs, 256, LDS_T128 + 2 * vec, s, a);
+        } else
+            hipLaunchKernelGGL((k_xattn_bwd<1, 4, 128, 3, 1>), grid4, 256, LDS_T128 + vec, s, a);
         if (S % 256) hipLaunchKernelGGL((k_xattn_bwd<0, 4, 128>), grid4, 256, LDS_T128, s, a);
         else hipLaunchKernelGGL((k_xattn_bwd<0, 8, 128>), (int)(B * H * (S / 256)), 512, LDS_T128, s, a);
     } else {                                              // head size 64: workgroups of 4 waves, two per CU (measured)
@@ -866,3 +1138,29 @@ extern "C" int ar_attn_bwd_exact(const void* Q, const void* K, const void* V, co
     }
     return launch_status();
 }
+
+#define XATTN_BWD_PARAMS                                                                                                                   \
+    const void *Q, const void *K, const void *V, const void *O, const void *dO, const float *LSE, void *dQ, void *dK, void *dV, int64_t B,   \
+        int64_t S, int64_t H, int64_t D, int64_t kv_rep, float scale, float bias_in, float bias_out, int64_t valid_len, int64_t q_bs,        \
+        int64_t q_hs, int64_t q_ts, int64_t k_bs, int64_t k_hs, int64_t k_ts, int64_t v_bs, int64_t v_hs, int64_t v_ts, int64_t o_bs,        \
+        int64_t o_hs, int64_t o_ts, int64_t do_bs, int64_t do_hs, int64_t do_ts, int64_t lddq, int64_t lddk, int64_t lddv, void *workspace,  \
+        int64_t workspace_bytes, ar_stream_t stream
+#define XATTN_BWD_ARGS                                                                                                                     \
+    Q, K, V, O, dO, LSE, dQ, dK, dV, B, S, H, D, kv_rep, scale, bias_in, bias_out, valid_len, q_bs, q_hs, q_ts, k_bs, k_hs, k_ts, v_bs, v_hs, \
+        v_ts, o_bs, o_hs, o_ts, do_bs, do_hs, do_ts, lddq, lddk, lddv, workspace, workspace_bytes, stream
+
+extern "C" int ar_attn_bwd_exact(XATTN_BWD_PARAMS) { return xattn_bwd_exact_launch(false, XATTN_BWD_ARGS); }
+
+extern "C" int ar_attn_bwd_exact_grouped(XATTN_BWD_PARAMS) { return xattn_bwd_exact_launch(true, XATTN_BWD_ARGS); }
+
+// the run of workgroup `block` of `workgroups` over `items` items, as the grouped kernel derives it (csrc/ar_attn_sched.hpp): host tests
+extern "C" int ar_attn_bwd_grouped_run(int64_t items, int64_t workgroups, int64_t block, int64_t* first, int64_t* count) {
+    if (items < 1 || workgroups < 1 || workgroups > items || block < 0 || block >= workgroups || items > 0x7fffffffLL || !first || !count)
+        return AR_ERR_UNSUPPORTED;
+    int f, c;
+    ar::xattn_group_run(ar::xattn_group_run_of_block((int)block, (int)workgroups), (int)workgroups, (int)items, f, c);
+    *first = f; *count = c;
+    return 0;
+}
+#undef XATTN_BWD_PARAMS
+#undef XATTN_BWD_ARGS

@@ -410,11 +410,14 @@ class ExactLlamaBlock(ExactBlockMixin, FusedLlamaBlock):
         self._dw_x("o", dx2, s.pop("a_in"))
         da = bq(self._dx_x("o", dx2), s.pop("a2d"), aq["o"])
         del dx2
-        gq4, gk4, gv4 = self._attention_backward(s.pop("attn"), da, B, S, self.attn.scaling)
-        del da
-        rope_graph = s.pop("rope_graph")
         nq, nk = hq * hd, hkv * hd
         dqkv = torch.empty((T, nq + 2 * nk), dtype=self.dtype, device=dy2d.device) if P["dw_qkv"] else None
+        # the first-party attention backward writes dV into its column slice of the merged gradient buffer (dQ and dK pass through the
+        # rotation's backward first)
+        outs = None if dqkv is None else (None, None, dqkv[:, nq + nk:])
+        gq4, gk4, gv4 = self._attention_backward(s.pop("attn"), da, B, S, self.attn.scaling, outs=outs)
+        del da
+        rope_graph = s.pop("rope_graph")
         slices = None if dqkv is None else (dqkv[:, :nq], dqkv[:, nq:nq + nk])
         if rope_graph is None:
             dq2d, dk2d = ops.rope_bwd_exact(gq4, gk4, s["cos"], s["sin"], S, hd, out=slices)
@@ -446,7 +449,8 @@ class ExactLlamaBlock(ExactBlockMixin, FusedLlamaBlock):
             else:
                 dq2d, dk2d = dq_raw, dk_raw
         if dqkv is not None:
-            dqkv[:, nq + nk:].view(B, S, hkv, hd).copy_(gv4.transpose(1, 2))
+            if gv4.untyped_storage().data_ptr() != dqkv.untyped_storage().data_ptr():      # (not written in place: torch's attention, or
+                dqkv[:, nq + nk:].view(B, S, hkv, hd).copy_(gv4.transpose(1, 2))          # a call the grouped kernel does not take)
             self._dw_x("qkv", dqkv, h1_in)
         else:
             dv2d = gv4.transpose(1, 2).reshape(T, nk)

@@ -185,14 +185,19 @@ def exact_attention_forward(q4, k4, v4, mask, scale, S, key_block=0):
 
 def exact_attention_backward(xa, dattn4, scale, outs=None):
     """gradients of the call `exact_attention_forward` made: -> (gq4 [B, H, S, D], gk4, gv4 [B, H / kv_rep, S, D]) -- the kv_rep query
-    heads of a group summed as autograd's expand backward does (one fp32 sum per value, rounded once).
-    outs (kv_rep == 1 only): three [B * S, H * D] destinations (column slices of a merged gradient buffer) the kernels write into."""
+    heads of a group summed as autograd's expand backward does (one fp32 sum per value, rounded once): inside the key-side kernel
+    at head size 128 with groups of up to 4, or of 8 (ops.attn_bwd_exact grouped), by torch's sum over the per-head results otherwise.
+    outs: (dq [B * S, H * D], dk, dv [B * S, (H / kv_rep) * D]) destinations the kernels write into (column slices of a merged
+    gradient buffer; any of them None: a fresh buffer); ignored on the path that sums per-head results."""
     q4, k4, v4, o4, lse, st = xa
     B, H, S, D = q4.shape
     hk = k4.shape[1]
-    kw = {}
-    if outs is not None and hk == H:
-        kw = dict(dq=outs[0], dk=outs[1], dv=outs[2])
+    kw = {} if outs is None else dict(dq=outs[0], dk=outs[1], dv=outs[2])
+    if hk < H:
+        got = ops.attn_bwd_exact(q4, k4, v4, o4, lse, dattn4, st, float(scale), grouped=True, **kw)
+        if got is not None:
+            return got[0].transpose(1, 2), got[1].transpose(1, 2), got[2].transpose(1, 2)
+        kw = {}
     got = ops.attn_bwd_exact(q4, k4, v4, o4, lse, dattn4, st, float(scale), **kw)
     if got is None:
         raise RuntimeError("ar_attn_bwd_exact refused a call whose forward it took")

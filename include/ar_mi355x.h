@@ -34,7 +34,7 @@ enum { AR_DT_BF16 = 0, AR_DT_F16 = 1, AR_DT_F32 = 2 };
 enum { AR_OK = 0, AR_ERR_UNSUPPORTED = -1 };
 
 /* ABI version of this header; bump on any signature change.  ar_abi_version() of the loaded library must equal it. */
-#define AR_ABI_VERSION 28
+#define AR_ABI_VERSION 29
 int ar_abi_version(void);
 /* Human-readable text for a non-zero return code of any function below. */
 const char* ar_error_string(int code);
@@ -493,6 +493,24 @@ int ar_attn_bwd_exact(const void* Q, const void* K, const void* V, const void* O
                       int64_t valid_len, int64_t q_bs, int64_t q_hs, int64_t q_ts, int64_t k_bs, int64_t k_hs, int64_t k_ts, int64_t v_bs,
                       int64_t v_hs, int64_t v_ts, int64_t o_bs, int64_t o_hs, int64_t o_ts, int64_t do_bs, int64_t do_hs, int64_t do_ts,
                       int64_t lddq, int64_t lddk, int64_t lddv, void* workspace, int64_t workspace_bytes, ar_stream_t stream);
+
+/* The same backward with the query-head groups of dK / dV SUMMED in the key-side kernel -- what autograd returns for the un-repeated
+ * k / v of transformers' repeat_kv (transformers/integrations/sdpa_attention.py: the expand backward's sum over the kv_rep heads of a
+ * group, one fp32 accumulation per value in ascending head order, rounded once).  Same operands; dK / dV are [B, S, H / kv_rep, D]
+ * with token strides lddk / lddv (0 = (H / kv_rep) * D; larger: column slices of a merged gradient buffer), dQ as above.  The key side
+ * is a persistent kernel: one workgroup per CU at the most, each with a fixed contiguous run of (batch, key head, 128-key block) items
+ * (ar_attn_bwd_grouped_run: the run of one workgroup, for host tests), per item the group's heads in ascending order with K / V loaded
+ * once.  workspace: ar_attn_bwd_exact_grouped_workspace_bytes(B, S, H, kv_rep) bytes, 16-byte aligned.  D == 128 and kv_rep <= 4 or
+ * kv_rep == 8 (torch's sum runs four accumulators, head j into accumulator j % 4: groups of 8 pair heads (j, j + 4) first, which the
+ * kernel restates); anything else AR_ERR_UNSUPPORTED, and the caller sums ar_attn_bwd_exact's heads. */
+int64_t ar_attn_bwd_exact_grouped_workspace_bytes(int64_t B, int64_t S, int64_t H, int64_t kv_rep);
+int ar_attn_bwd_exact_grouped(const void* Q, const void* K, const void* V, const void* O, const void* dO, const float* LSE, void* dQ,
+                              void* dK, void* dV, int64_t B, int64_t S, int64_t H, int64_t D, int64_t kv_rep, float scale, float bias_in,
+                              float bias_out, int64_t valid_len, int64_t q_bs, int64_t q_hs, int64_t q_ts, int64_t k_bs, int64_t k_hs,
+                              int64_t k_ts, int64_t v_bs, int64_t v_hs, int64_t v_ts, int64_t o_bs, int64_t o_hs, int64_t o_ts,
+                              int64_t do_bs, int64_t do_hs, int64_t do_ts, int64_t lddq, int64_t lddk, int64_t lddv, void* workspace,
+                              int64_t workspace_bytes, ar_stream_t stream);
+int ar_attn_bwd_grouped_run(int64_t items, int64_t workgroups, int64_t block, int64_t* first, int64_t* count);
 
 /* ---- causal attention backward, head size 64 (deterministic: two MFMA kernels, no float atomics) ---------------------------
  * replaces: autograd of the same attention call -- torch's aten::_scaled_dot_product_efficient_attention_backward, i.e. aiter's
