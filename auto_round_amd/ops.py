@@ -696,7 +696,8 @@ def attn_fwd_exact(q4: torch.Tensor, k4: torch.Tensor, v4: torch.Tensor, mask_st
     q4 [B, H, S, D], k4 / v4 [B, H / kv_rep, S, D]: bf16 views with unit stride along D (token-major or head-major).
     mask_struct = (bias_in, bias_out, valid_len) from `mask_structure`.  key_block: keys per online-softmax step (0 = the tuning
     minibatch's; 16 / 32 / 64: the library's other configurations, see the header).  -> (out [B, S, H, D] contiguous, lse [B, H, S] fp32), or
-    None when the kernel does not take the call (the caller keeps torch's SDPA)."""
+    None when the kernel does not take the call (the caller keeps torch's SDPA): other head sizes than 64 / 128, S % 128, and head
+    size 64 at S = 128, where the backward does not have the library's bits (so neither launcher takes the shape)."""
     if mask_struct is None or q4.dim() != 4 or q4.dtype != torch.bfloat16 or k4.dtype != q4.dtype or v4.dtype != q4.dtype:
         return None
     B, H, S, D = (int(x) for x in q4.shape)

@@ -471,7 +471,8 @@ int ar_attn_fwd_masked(const void* Q, const void* K, const void* V, void* O, flo
  *           structured mask; both values must be bf16 numbers.  key_block: the keys per online-softmax step -- the one tile size of the
  *           library's configuration the bits depend on (it picks the configuration by sequence length and head size): 0 = the tuning
  *           minibatch's (64 at head size 128, 32 at 64; what the library uses for S = 1024 .. 2048, at head size 128 also 4096), or 16 /
- *           32 / 64 (callers try them in their proof: auto_round_amd/exact_block.py).  D in {64, 128}, S % 128 == 0; anything else
+ *           32 / 64 (callers try them in their proof: auto_round_amd/exact_block.py).  D in {64, 128}, S % 128 == 0, and S >= 256 at
+ *           head size 64 (the backward below does not have the library's bits at S = 128 there, so the pair refuses it); anything else
  *           AR_ERR_UNSUPPORTED. */
 int ar_attn_fwd_exact(const void* Q, const void* K, const void* V, void* O, float* LSE, int64_t B, int64_t S, int64_t H, int64_t D,
                       int64_t kv_rep, float scale, float bias_in, float bias_out, int64_t valid_len, int64_t q_bs, int64_t q_hs,
@@ -480,13 +481,16 @@ int ar_attn_fwd_exact(const void* Q, const void* K, const void* V, void* O, floa
 
 /* The matching BACKWARD with the library's bits: what aten::_scaled_dot_product_efficient_attention_backward returns for the same call
  * on this stack (AOTriton 0.11.1 bwd_preprocess + bwd_kernel_dk_dv + bwd_kernel_dq with an additive bias; autograd of the call
- * ar_attn_fwd_exact replaces; the arithmetic -- delta in the library's lane order, scores accumulated on top of fl(bias / sm_scale),
+ * ar_attn_fwd_exact replaces; the arithmetic -- delta in the library's lane order, scores accumulated on top of
+ * fl(bias * fl(1 / sm_scale)) (the product, not fl(bias / sm_scale): a bias of 3.0 or 0.8125 tells them apart at head size 128),
  * p = exp2(fma(..)) with the one non-fused element of the key-side kernel, natural / adopted k orders of the accumulating products -- is
  * in csrc/ar_attn_exact.hip).  Q / K / V / O / dO bf16 with element strides (batch, head, token), K / V grouped as in the forward;
  * O / LSE are the forward's results.  dQ, dK, dV are written token-major [B, S, H, D] with token strides lddq / lddk / lddv (0 = H * D;
  * larger strides: column slices of a merged buffer); dK / dV hold one gradient per QUERY head -- the caller adds the kv_rep heads of a
  * group, as autograd's expand backward does.  workspace: ar_attn_bwd_exact_workspace_bytes(B, S, H) bytes.  D in {64, 128},
- * S % 128 == 0, S <= 4096; anything else AR_ERR_UNSUPPORTED.  Equality with the library is proven per call signature by the caller. */
+ * S % 128 == 0, S <= 4096, and S >= 256 at head size 64 (at S = 128 the library's backward runs a configuration this kernel does not
+ * restate: a few dq / dk / dv values in 100 000 differ); anything else AR_ERR_UNSUPPORTED.  Equality with the library is proven per call
+ * signature by the caller. */
 int64_t ar_attn_bwd_exact_workspace_bytes(int64_t B, int64_t S, int64_t H);
 int ar_attn_bwd_exact(const void* Q, const void* K, const void* V, const void* O, const void* dO, const float* LSE, void* dQ, void* dK,
                       void* dV, int64_t B, int64_t S, int64_t H, int64_t D, int64_t kv_rep, float scale, float bias_in, float bias_out,

@@ -110,3 +110,11 @@ def test_refusals():
     assert ops.attn_fwd_exact(q, k, v, (0.3, 0.0, 255), 1.0) is None                             # mask value not a bf16 number
     hard = (0.0, float(torch.finfo(torch.bfloat16).min), 255)
     assert ops.attn_fwd_exact(q, k, v, hard, 1.0) is None                                        # hard (-inf like) mask
+    q1, k1, v1, mask1 = _case(1, 2, 128, 64, 2, 0.35)                                            # head size 64 at S = 128: the backward
+    st1 = ops.mask_structure(mask1, 128)                                                         # does not have the library's bits there
+    assert st1 == (1.0, 0.0, 127)
+    assert ops.attn_fwd_exact(q1, k1, v1, st1, 1.0, key_block=ops.attn_key_block_guess(64, 128)) is None
+    o1 = torch.zeros(1, 128, 2, 64, device="cuda", dtype=torch.bfloat16)
+    lse1 = torch.zeros(1, 2, 128, device="cuda")
+    assert ops.attn_bwd_exact(q1, k1, v1, o1, lse1, o1, st1, 1.0) is None
+    assert ops.attn_fwd_exact(q, k, v, st, 1.0, key_block=ops.attn_key_block_guess(64, 256)) is not None          # S = 256 is taken
